@@ -2,6 +2,9 @@
 
   python bench.py --gpus N --steps K --warmup W [--config acdc|synapse|ham512]
                                                    (N > 1: launched by torch.distributed.run, one rank per GPU)
+  --dump-outputs DIR   rank 0 writes what the last timed step computed (loss, logits, updated parameters, gradients) as
+                       DIR/<name>.npy in float32, right after the timed loop.  That step starts from the restored start state
+                       (_StartState), so with the same arguments its inputs are the same in every run
 
 A "step" = the reference's train-step body (src/main_acdc.py:237-257) on one synthetic batch already resident in
 HBM: zero_grad -> CENet forward -> Dice+CE (0.5/0.5) -> backward -> gradient all-reduce (RCCL) -> fused SGD.
@@ -99,7 +102,14 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true", help="skip the instrumented passes (roofline, roofline_stages)")
     ap.add_argument("--cpu-steps", type=int, default=3)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, logits, updated parameters, "
+                         "gradients) as DIR/<name>.npy in float32; the last step starts from the restored start state "
+                         "(rank 0; see dump_outputs, _StartState)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def make_model(dev, cfg=None):
@@ -564,6 +574,43 @@ def _time_steps(fn, n):
     return (time.perf_counter() - t0) / n
 
 
+DUMP_CAP = 1 << 22  # elements per dumped array (16 MB of float32): loss + logits + parameters + gradients stay under 64 MB
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every tensor of `arrays` as float32 `d/<name>.npy`.  One with more than DUMP_CAP elements is flattened and
+    sampled at DUMP_CAP positions drawn by a fixed seed and sorted, the same positions for every run at the same shape, so that
+    the dumps of two builds compare element for element."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float().cpu()
+        if t.numel() > DUMP_CAP:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_CAP].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(d, f"{name}.npy"), t.numpy())
+
+
+class _StartState:
+    """--dump-outputs: the training state before the first step (parameters, momentum, BatchNorm buffers), restored in place
+    (the captured graphs keep their addresses) before the LAST timed step, so that the step whose outputs are dumped starts from
+    the same inputs in every run.  Without it those inputs are the end of the run's earlier steps, whose reductions end in float
+    atomics (CENET_DETERMINISTIC not built): their last bits change from run to run and grow with every step."""
+
+    def __init__(self, net, arena, opt):
+        self.net, self.arena, self.opt = net, arena, opt
+        self.params, self.buf = arena.params.clone(), opt.buf.clone()
+        self.buffers = [b.clone() for b in net.buffers()]
+
+    def restore(self):
+        with torch.no_grad():
+            self.arena.params.copy_(self.params)
+            self.arena.refresh_shadow()  # the bf16 GEMM operands are a cast of the parameters
+            self.opt.buf.copy_(self.buf)
+            for b, s in zip(self.net.buffers(), self.buffers):
+                b.copy_(s)
+
+
 def dist_identity(dev, world):
     """What makes an N > 1 line self-proving: the collective backend, its version, and how many DISTINCT GPUs the ranks really
     sit on (every rank contributes its device's PCI identity / UUID; a launch that put two ranks on one device, or one that fell
@@ -626,12 +673,22 @@ def main():
     sched = optim.PolyLR(opt, max_iterations=100000)
     crit = losses.Criterion(cfg["classes"], argparse.Namespace(loss_type="dice,ce", loss_weights="0.5,0.5"))
     x, lab = synthetic(B, dev, seed=1234 + rank, cfg=cfg)
+    start = _StartState(net, arena, opt) if a.dump_outputs else None
 
     comm = [True]  # (False: rank 0's instrumented passes at N > 1 — the other ranks are not in the step, so no collective)
+    # --dump-outputs: the logits of the latest forward, and per captured step object the static logits tensor of its capture
+    # (every replay rewrites it in place)
+    last = {}
+    captured = {}
+
+    def forward_loss():
+        logits = net(x)
+        last["logits"] = logits.detach()
+        return crit(logits, lab)
 
     def body(sync_hyper=True, after_backward=None):
         opt.zero_grad()
-        loss = crit(net(x), lab)
+        loss = forward_loss()
         loss.backward()
         if after_backward is not None:  # (instrumented passes only)
             after_backward()
@@ -642,7 +699,7 @@ def main():
 
     def fwd_bwd():
         opt.zero_grad()
-        loss = crit(net(x), lab)
+        loss = forward_loss()
         loss.backward()
         return loss
 
@@ -661,6 +718,7 @@ def main():
         try:
             ops.set_wgrad_overlap(False)
             graphed = GraphedStep(lambda: body(sync_hyper=False), optimizer=opt, warmup=2)
+            captured[graphed] = last["logits"]
         except Exception as e:  # capture is an optimisation: fall back to eager launches of the same kernels
             if a.graph == "on":
                 raise
@@ -695,10 +753,11 @@ def main():
         parallel.attach(net, None)  # no hooks inside the captures: the step objects drive the reducer themselves
         ops.set_wgrad_overlap(False)
         for name, make in (("split", lambda: GraphedSplitStep(fwd_bwd, opt, reducer.finish, warmup=2)),
-                           ("segmented", lambda: SegmentedStep(net, lambda: crit(net(x), lab), opt, reducer.segment_ready,
+                           ("segmented", lambda: SegmentedStep(net, forward_loss, opt, reducer.segment_ready,
                                                                reducer.finish, warmup=2))):
             try:
                 cands[name] = make()
+                captured[cands[name]] = last["logits"]
             except Exception as e:
                 print(f"[bench] {name} hipGraph capture failed on rank {rank} ({type(e).__name__}: {e})", file=sys.stderr)
                 torch.cuda.synchronize()
@@ -759,7 +818,13 @@ def main():
     torch.cuda.synchronize()
     WATCHDOG.beat("timed loop")
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for i in range(a.steps):
+        if start is not None and i == a.steps - 1:  # off the clock: drain the queue, restore the start state
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            start.restore()
+            torch.cuda.synchronize()
+            t0 += time.perf_counter() - t1
         loss = step()
     torch.cuda.synchronize()
     if use_dist:
@@ -771,6 +836,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     final_loss = float(loss.item())
+    if a.dump_outputs and rank == 0:  # before the instrumented passes below, which run more steps on the same parameters
+        dump_outputs(a.dump_outputs, {"loss": loss, "logits": captured[graphed] if graphed is not None else last["logits"],
+                                      "params": arena.params, "grads": arena.grads})
 
     if rank == 0:
         ms = dt / a.steps * 1e3
