@@ -4,8 +4,8 @@ The reference writes `torch.save(net.state_dict(), 'best.pth')` (src/main_acdc.p
 `net.load_state_dict(torch.load(path, weights_only=True))` (main_acdc.py:152-160); `cenet_amd.networks.CENet` keeps the
 reference's 801 state-dict keys, so those files load here unchanged and files written here load in the reference
 (`save_weights` / `load_weights`).  The reference keeps no optimizer or scheduler state, so it cannot resume a run;
-`save_training_state` / `load_training_state` add that: weights + the SGD momentum arena + step counters + the poly-LR
-position, in one file whose `"model"` entry is again a plain reference-compatible state dict.
+`save_training_state` / `load_training_state` add that: weights + the optimizer state (SGD momentum or Adam's two moments, per
+parameter name) + step counters + the LR schedule's position, in one file whose `"model"` entry is again a plain reference-compatible state dict.
 """
 from __future__ import annotations
 
@@ -31,23 +31,34 @@ def save_training_state(path: str, net: torch.nn.Module, optimizer=None, schedul
     state = {"model": {k: v.detach().cpu() for k, v in net.state_dict().items()}}
     if optimizer is not None:
         osd = optimizer.state_dict()
-        state["optimizer"] = {"momentum": {n: v.detach().cpu() for n, v in osd["momentum"].items()}, "steps": int(osd["steps"]),
-                              "lr": float(osd["lr"])}
+        # per-parameter state (FusedSGD: "momentum"; FusedAdam / FusedAdamW: "kind", "exp_avg", "exp_avg_sq") as CPU tensors
+        state["optimizer"] = {k: ({n: t.detach().cpu() for n, t in v.items()} if isinstance(v, dict) else v)
+                              for k, v in osd.items() if k not in ("steps", "lr")}
+        state["optimizer"].update(steps=int(osd["steps"]), lr=float(osd["lr"]))
     if scheduler is not None:
-        state["scheduler"] = {"last_epoch": int(scheduler.last_epoch), "base_lr": float(scheduler.base_lr)}
+        if hasattr(scheduler, "state_dict"):  # cosine / exp / step / custom: their kind is recorded
+            state["scheduler"] = scheduler.state_dict()
+        else:  # PolyLR
+            state["scheduler"] = {"last_epoch": int(scheduler.last_epoch), "base_lr": float(scheduler.base_lr)}
     if extra:
         state["extra"] = dict(extra)
     torch.save(state, path)
 
 
 def load_training_state(path: str, net: torch.nn.Module, optimizer=None, scheduler=None) -> dict:
-    """Restores weights (in place: the optimizer's parameter arena keeps pointing at them), momentum, counters, LR."""
+    """Restores weights (in place: the optimizer's parameter arena keeps pointing at them), optimizer state, counters, LR.
+    A state written by another optimizer or schedule kind is refused (ValueError)."""
     state = torch.load(path, map_location="cpu", weights_only=True)
     net.load_state_dict(state["model"], strict=True)
     if optimizer is not None and "optimizer" in state:
         o = state["optimizer"]
         optimizer.load_state_dict(o)
     if scheduler is not None and "scheduler" in state:
-        scheduler.last_epoch = state["scheduler"]["last_epoch"]
-        scheduler.base_lr = state["scheduler"]["base_lr"]
+        if hasattr(scheduler, "load_state_dict"):
+            scheduler.load_state_dict(state["scheduler"])
+        elif "kind" in state["scheduler"]:
+            raise ValueError(f"training state of a {state['scheduler']['kind']} schedule loaded into {type(scheduler).__name__}")
+        else:
+            scheduler.last_epoch = state["scheduler"]["last_epoch"]
+            scheduler.base_lr = state["scheduler"]["base_lr"]
     return state.get("extra", {})

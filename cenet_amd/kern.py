@@ -1008,6 +1008,16 @@ def sgd_step(p, g, buf, hyper5, n, shadow=None):
         _lib.check(rc, "cenet_sgd_step_shadow_f32")
 
 
+def adam_step(p, g, exp_avg, exp_avg_sq, hyper12, n, shadow=None):
+    """fused Adam / AdamW update (hyper12: include/cenet_hip.h); shadow: bf16 copy of the parameters, rewritten in the same pass"""
+    _chk(p, g, exp_avg, exp_avg_sq, hyper12, shadow)
+    if shadow is None:
+        _call("cenet_adam_step_f32", p, g, exp_avg, exp_avg_sq, hyper12, L(n))
+    else:
+        rc = _lib.lib().cenet_adam_step_shadow_f32(P(p), P(g), P(exp_avg), P(exp_avg_sq), P(hyper12), L(n), P(shadow), stream())
+        _lib.check(rc, "cenet_adam_step_shadow_f32")
+
+
 def cast(x: torch.Tensor, dtype) -> torch.Tensor:
     """fp32 <-> bf16 copy of a contiguous tensor (cenet_cast_*); returns x itself when it already has `dtype`"""
     if x.dtype == dtype:

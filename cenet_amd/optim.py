@@ -1,15 +1,19 @@
-"""Flat parameter/gradient arena, fused SGD and the poly LR schedule.
+"""Flat parameter/gradient arena, the fused optimizers and the LR schedules.
 
-Mirrors the reference's optimiser plumbing (src/utils/core.py:12-41: torch.optim.SGD(lr, momentum 0.9, weight_decay)
-and LambdaLR (1 - it/max)^0.9) on top of ONE contiguous fp32 buffer for parameters, one for gradients and one for
-momentum, so that per step there is one memset, one fused update kernel and a handful of large all-reduces instead
-of 630 small ones.  `torch.optim.SGD(net.parameters())` keeps working on arena-backed parameters
-(their `.data` / `.grad` are views), so the reference's `get_optimizer` can also be used unchanged.
+Mirrors the reference's optimiser plumbing (src/utils/core.py:12-41: `get_optimizer` — torch.optim.SGD(lr, momentum 0.9,
+weight_decay), Adam, AdamW — and `get_scheduler` — poly, cosine, exp, step, custom) on top of ONE contiguous fp32 buffer for
+parameters, one for gradients and one per optimizer state (momentum; Adam's two moments), so that per step there is one
+memset, one fused update kernel and a handful of large all-reduces instead of 630 small ones.
+`get_optimizer` / `get_scheduler` here take the reference's arguments and strings.  `torch.optim.SGD(net.parameters())` keeps
+working on arena-backed parameters (their `.data` / `.grad` are views), so the reference's `get_optimizer` can also be used
+unchanged.
 """
 from __future__ import annotations
 
+import math
 from typing import Callable, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -88,8 +92,8 @@ class ParamArena:
             p._cenet_arena_slot = (self, o)
 
     def enable_shadow(self):
-        """One flat bf16 copy of `params`; every parameter's `_cenet_shadow` is a view into it.  `FusedSGD.step` rewrites it
-        in the same kernel that updates the fp32 master copy."""
+        """One flat bf16 copy of `params`; every parameter's `_cenet_shadow` is a view into it.  The fused optimizers' step rewrites
+        it in the same kernel that updates the fp32 master copy."""
         if self.shadow is not None:
             return
         self.shadow = torch.empty(self.numel, device=self.params.device, dtype=torch.bfloat16)
@@ -129,6 +133,38 @@ class ParamArena:
         return self.grads[s:e]
 
 
+class _HyperStage:
+    """Uploads a fused optimizer's hyper-parameters (a few fp32 values) into its device buffer.
+
+    On the GPU the copy is asynchronous from PINNED staging (a pageable temporary could be recycled by the host before the copy
+    executes when the host runs ahead of the GPU, e.g. under hipGraph replay).  4 slots rotate; a slot is reused only after the
+    copy that last read it has executed (its event), which also bounds how far the host can run ahead of the GPU: 4 steps."""
+
+    def __init__(self, n: int, slots: int = 4):
+        self.n, self.slots = n, slots
+        self._stage = None
+
+    def upload(self, hyper: torch.Tensor, vals: Sequence[float]):
+        if not hyper.is_cuda:
+            hyper.copy_(torch.tensor(vals, dtype=torch.float32))
+            return
+        if self._stage is None:
+            self._stage = [torch.zeros(self.n, dtype=torch.float32).pin_memory() for _ in range(self.slots)]
+            self._stage_ev = [None] * self.slots
+            self._slot = 0
+        i = self._slot
+        self._slot = (i + 1) % self.slots
+        if self._stage_ev[i] is not None:
+            self._stage_ev[i].synchronize()
+        h = self._stage[i]
+        for j, v in enumerate(vals):
+            h[j] = v
+        hyper.copy_(h, non_blocking=True)
+        if self._stage_ev[i] is None:
+            self._stage_ev[i] = torch.cuda.Event()
+        self._stage_ev[i].record()
+
+
 class FusedSGD:
     """torch.optim.SGD(momentum, weight_decay, dampening 0, nesterov False) semantics, one kernel launch per step."""
 
@@ -141,6 +177,7 @@ class FusedSGD:
         self.grad_scale = grad_scale
         self.buf = torch.zeros_like(arena.params)
         self.hyper = torch.zeros(5, device=arena.params.device, dtype=torch.float32)
+        self._stage = _HyperStage(5)
         self._steps = 0
         self._sync_hyper()
 
@@ -153,28 +190,7 @@ class FusedSGD:
 
     def _sync_hyper(self):
         vals = [self.lr, self.momentum, self.weight_decay, self.grad_scale, 1.0 if self._steps == 0 else 0.0]
-        if self.hyper.is_cuda:
-            # asynchronous upload from PINNED staging (a pageable temporary could be recycled by the host before the copy
-            # executes when the host runs ahead of the GPU, e.g. under hipGraph replay).  4 slots rotate; a slot is reused
-            # only after the copy that last read it has executed (its event), which also bounds how far the host can run
-            # ahead of the GPU: 4 steps.
-            if not hasattr(self, "_stage"):
-                self._stage = [torch.zeros(5, dtype=torch.float32).pin_memory() for _ in range(4)]
-                self._stage_ev = [None] * 4
-                self._slot = 0
-            i = self._slot
-            self._slot = (i + 1) % len(self._stage)
-            if self._stage_ev[i] is not None:
-                self._stage_ev[i].synchronize()
-            h = self._stage[i]
-            for j, v in enumerate(vals):
-                h[j] = v
-            self.hyper.copy_(h, non_blocking=True)
-            if self._stage_ev[i] is None:
-                self._stage_ev[i] = torch.cuda.Event()
-            self._stage_ev[i].record()
-        else:
-            self.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
+        self._stage.upload(self.hyper, vals)
 
     def zero_grad(self, set_to_none: bool = False):
         self.arena.zero_grad()
@@ -217,6 +233,129 @@ class FusedSGD:
             raise ValueError("training state without per-parameter momentum ('momentum': name -> tensor); re-save it")
         self._steps, self.lr = sd["steps"], sd["lr"]
 
+    def state_buffers(self) -> List[torch.Tensor]:
+        """the flat per-parameter state (what a caller snapshots around a capture's warm-up steps)"""
+        return [self.buf]
+
+
+class FusedAdam:
+    """torch.optim.Adam (`decoupled=False`) / AdamW (`decoupled=True`) semantics — amsgrad, maximize off — over the arena, one
+    kernel launch per step (csrc/adam.hip).  The same contract as FusedSGD: one persistent `param_groups[0]` (lr, betas, eps,
+    weight_decay) read at every step, `grad_scale` (GradReducer's 1/world), `prepare()` / `step(sync_hyper=False)` for captured
+    steps, `_steps`.  The bias corrections of step t = `_steps + 1` are computed on the host in double when the hyper-parameters
+    are uploaded (step() or prepare()), so a graph replay preceded by prepare() advances them."""
+
+    kind = "adam"
+    decoupled = False
+
+    def __init__(self, arena: ParamArena, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, grad_scale: float = 1.0, *, amsgrad: bool = False, maximize: bool = False,
+                 capturable: bool = False, differentiable: bool = False, foreach: Optional[bool] = None,
+                 fused: Optional[bool] = None):
+        # options of torch.optim.Adam that the reference never sets are refused, not ignored
+        for name, val in (("amsgrad", amsgrad), ("maximize", maximize), ("capturable", capturable),
+                          ("differentiable", differentiable)):
+            if val:
+                raise ValueError(f"{type(self).__name__}: {name}=True is not supported")
+        for name, val in (("foreach", foreach), ("fused", fused)):
+            if val is not None:
+                raise ValueError(f"{type(self).__name__}: {name}= selects a torch implementation; the arena has its own kernel")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"Invalid beta parameters: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        self.arena = arena
+        self.param_groups = [{"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": weight_decay,
+                              "params": arena._plist}]
+        self.grad_scale = grad_scale
+        self.exp_avg = torch.zeros_like(arena.params)
+        self.exp_avg_sq = torch.zeros_like(arena.params)
+        self.hyper = torch.zeros(12, device=arena.params.device, dtype=torch.float32)
+        self._stage = _HyperStage(12)
+        self._steps = 0
+        self._sync_hyper()
+
+    lr = property(lambda self: self.param_groups[0]["lr"], lambda self, v: self.param_groups[0].__setitem__("lr", v))
+    betas = property(lambda self: self.param_groups[0]["betas"],
+                     lambda self, v: self.param_groups[0].__setitem__("betas", tuple(v)))
+    eps = property(lambda self: self.param_groups[0]["eps"], lambda self, v: self.param_groups[0].__setitem__("eps", v))
+    weight_decay = property(lambda self: self.param_groups[0]["weight_decay"],
+                            lambda self, v: self.param_groups[0].__setitem__("weight_decay", v))
+
+    def _sync_hyper(self):
+        # torch's _single_tensor_adam: the step counter t, the bias corrections and step_size in Python (double) arithmetic
+        lr, (b1, b2), eps, wd = self.lr, self.betas, self.eps, self.weight_decay
+        t = float(self._steps + 1)
+        bias_correction1 = 1 - b1 ** t
+        bias_correction2 = 1 - b2 ** t
+        step_size = lr / bias_correction1
+        bias_correction2_sqrt = bias_correction2 ** 0.5
+        vals = [lr, b1, b2, eps, wd, self.grad_scale, step_size, bias_correction2_sqrt, 1.0 if self.decoupled else 0.0,
+                1 - b1, 1 - b2, 1 - lr * wd]
+        self._stage.upload(self.hyper, vals)
+
+    def zero_grad(self, set_to_none: bool = False):
+        self.arena.zero_grad()
+
+    def set_lr(self, lr: float):
+        self.lr = lr
+
+    def step(self, sync_hyper: bool = True):
+        """sync_hyper=False: the caller has uploaded the hyper-parameters of this step already (`prepare()`), as a captured step
+        must (no host->device copy inside a captured region)."""
+        if sync_hyper:
+            self._sync_hyper()
+        from . import ops
+        ops.wgrad_join()  # weight gradients issued on the side stream (ops._wgrad_side) must have landed
+        kern.adam_step(self.arena.params, self.arena.grads, self.exp_avg, self.exp_avg_sq, self.hyper, self.arena.numel,
+                       self.arena.shadow)
+        self._steps += 1
+
+    def prepare(self):
+        """Upload lr / betas / eps / wd / grad_scale and the bias corrections of the NEXT step (call before a graph replay)."""
+        self._sync_hyper()
+
+    def state_dict(self):
+        """`exp_avg` / `exp_avg_sq` per parameter NAME (the flat layout may differ between the saving and the loading run), the
+        step counter (the bias corrections continue from it), lr and the optimizer kind"""
+        idx = self.arena.index
+        return {"kind": self.kind,
+                "exp_avg": {n: self.exp_avg[o:o + k].detach().clone() for n, (o, k) in idx.items()},
+                "exp_avg_sq": {n: self.exp_avg_sq[o:o + k].detach().clone() for n, (o, k) in idx.items()},
+                "steps": self._steps, "lr": self.lr}
+
+    def load_state_dict(self, sd):
+        kind = sd.get("kind", "sgd" if "momentum" in sd else None)
+        if kind != self.kind:
+            raise ValueError(f"{type(self).__name__}.load_state_dict: the state was written by a {kind or 'different'} "
+                             f"optimizer, not {self.kind}")
+        idx = self.arena.index
+        for key, buf in (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
+            missing = [n for n in idx if n not in sd[key]]
+            if missing:
+                raise KeyError(f"{key} missing for parameters {missing[:5]}")
+            for n, (o, k) in idx.items():
+                buf[o:o + k].copy_(sd[key][n].reshape(-1).to(buf.device))
+        self._steps, self.lr = sd["steps"], sd["lr"]
+
+    def state_buffers(self) -> List[torch.Tensor]:
+        return [self.exp_avg, self.exp_avg_sq]
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW: decoupled weight decay (p *= 1 - lr wd before the Adam update); torch's default weight_decay 1e-2"""
+
+    kind = "adamw"
+    decoupled = True
+
+    def __init__(self, arena: ParamArena, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 1e-2, grad_scale: float = 1.0, **kw):
+        super().__init__(arena, lr, betas, eps, weight_decay, grad_scale, **kw)
+
 
 class PolyLR:
     """core.py:31: lr = base * (1 - step / max_iterations) ** 0.9 (LambdaLR semantics: step() after optimizer.step())."""
@@ -232,6 +371,160 @@ class PolyLR:
     def step(self):
         self.last_epoch += 1
         self.opt.set_lr(self.base_lr * (1 - self.last_epoch / self.max_it) ** self.power)
+
+
+class _FusedLRSchedule:
+    """Base of the cosine / exp / step / custom schedules (PolyLR's interface plus a kind-checked state_dict).  step() advances
+    `last_epoch` and derives the next lr from the optimizer's present one: cosine, exp and step are the recursive forms of torch
+    2.10's `get_lr()`, so long runs agree with torch to the last bit, and a resumed run continues from the lr restored with the
+    optimizer's state.  Works on any fused optimizer (anything with `lr` and `set_lr`), stepped once per iteration after
+    optimizer.step()."""
+
+    kind = ""
+
+    def __init__(self, optimizer):
+        self.opt = optimizer
+        self.base_lr = optimizer.lr
+        self.last_epoch = 0
+
+    def get_last_lr(self) -> List[float]:
+        return [self.opt.lr]
+
+    def step(self):
+        self.last_epoch += 1
+        self.opt.set_lr(self._next_lr(self.opt.lr))
+
+    def _next_lr(self, lr: float) -> float:
+        raise NotImplementedError
+
+    def state_dict(self) -> dict:
+        return {"kind": self.kind, "last_epoch": self.last_epoch, "base_lr": self.base_lr}
+
+    def load_state_dict(self, sd: dict):
+        if sd.get("kind") != self.kind:
+            raise ValueError(f"{type(self).__name__}.load_state_dict: the state was written by a "
+                             f"{sd.get('kind') or 'poly'} schedule, not {self.kind}")
+        self.last_epoch, self.base_lr = int(sd["last_epoch"]), float(sd["base_lr"])
+
+
+class CosineLR(_FusedLRSchedule):
+    """core.py:28: torch CosineAnnealingLR(T_max=max_iterations), eta_min 0 — its recursive form"""
+
+    kind = "cosine"
+
+    def __init__(self, optimizer, T_max: int, eta_min: float = 0.0):
+        super().__init__(optimizer)
+        self.T_max, self.eta_min = T_max, eta_min
+
+    def _next_lr(self, lr):
+        e, T, lo = self.last_epoch, self.T_max, self.eta_min
+        if (e - 1 - T) % (2 * T) == 0:
+            return lr + (self.base_lr - lo) * (1 - math.cos(math.pi / T)) / 2
+        return (1 + math.cos(math.pi * e / T)) / (1 + math.cos(math.pi * (e - 1) / T)) * (lr - lo) + lo
+
+
+class ExponentialLR(_FusedLRSchedule):
+    """core.py:32: torch ExponentialLR(gamma=0.95): lr *= gamma per step"""
+
+    kind = "exp"
+
+    def __init__(self, optimizer, gamma: float = 0.95):
+        super().__init__(optimizer)
+        self.gamma = gamma
+
+    def _next_lr(self, lr):
+        return lr * self.gamma
+
+
+class StepLR(_FusedLRSchedule):
+    """core.py:34: torch StepLR(step_size=200, gamma=0.5): lr *= gamma every step_size steps"""
+
+    kind = "step"
+
+    def __init__(self, optimizer, step_size: int = 200, gamma: float = 0.5):
+        super().__init__(optimizer)
+        self.step_size, self.gamma = step_size, gamma
+
+    def _next_lr(self, lr):
+        if self.last_epoch == 0 or self.last_epoch % self.step_size != 0:
+            return lr
+        return lr * self.gamma
+
+
+class CustomLR(_FusedLRSchedule):
+    """core.py:191-212 (CustomLR): a linear ramp from lr_start_high to lr_end_high over the first T_first steps, then a cosine
+    from lr_start_low to lr_end_low over max_epochs - T_first steps, in closed form from `last_epoch`.  The reference steps it
+    once per ITERATION while get_scheduler feeds it args.max_epochs (core.py:36-37, main_acdc.py:257), so its "epochs" are
+    iterations; kept as the reference runs it.  Like any torch scheduler it sets the optimizer's lr to its value at step 0 when
+    it is created (lr_start_high, 10x the base lr in get_scheduler)."""
+
+    kind = "custom"
+
+    def __init__(self, optimizer, T_first: int = 3, lr_start_high: float = 0.01, lr_end_high: float = 0.005,
+                 lr_start_low: float = 0.001, lr_end_low: float = 0.00001, max_epochs: int = 50):
+        super().__init__(optimizer)
+        self.T_first, self.max_epochs = T_first, max_epochs
+        self.lr_start_high, self.lr_end_high = lr_start_high, lr_end_high
+        self.lr_start_low, self.lr_end_low = lr_start_low, lr_end_low
+        optimizer.set_lr(self._next_lr(None))
+
+    def _next_lr(self, lr):
+        if self.last_epoch < self.T_first:
+            progress = self.last_epoch / self.T_first
+            return self.lr_start_high - (self.lr_start_high - self.lr_end_high) * progress
+        progress = (self.last_epoch - self.T_first) / (self.max_epochs - self.T_first)
+        # (numpy's cos, as the reference evaluates it)
+        return float(self.lr_start_low - (self.lr_start_low - self.lr_end_low) * (0.5 * (1 - np.cos(np.pi * progress))))
+
+
+def _arena_of(model: nn.Module) -> Optional[ParamArena]:
+    """the ParamArena that already holds every trainable parameter of `model`, None if none does"""
+    slots = [getattr(p, "_cenet_arena_slot", None) for p in model.parameters() if p.requires_grad]
+    arenas = {id(s[0]): s[0] for s in slots if s is not None}
+    if not arenas:
+        return None
+    if len(arenas) > 1 or any(s is None for s in slots):
+        raise ValueError("get_optimizer: the model's parameters are split between arenas (or only partly in one)")
+    return next(iter(arenas.values()))
+
+
+def get_optimizer(model: nn.Module, args):
+    """core.py:12-24 on the arena: args.optimizer in {'SGD', 'Adam', 'AdamW'} (any case), args.base_lr, args.weight_decay ->
+    FusedSGD(momentum 0.9) / FusedAdam / FusedAdamW (betas (0.9, 0.999), eps 1e-8).  The parameters are re-homed into a
+    ParamArena laid out by cenet_segments() (one segment for a model whose parameter names are not CENet's) unless they already
+    live in one, which is then used as it is."""
+    name = args.optimizer.lower()
+    if name not in ("adam", "adamw", "sgd"):
+        raise NotImplementedError(f"Optimizer {args.optimizer} not implemented")
+    arena = _arena_of(model)
+    if arena is None:
+        names = [n for n, p in model.named_parameters() if p.requires_grad]
+        segs = cenet_segments()
+        covered = all(any(pred(n) for _, pred in segs) for n in names)
+        arena = ParamArena(model, segs if covered else None)
+    if name == "adam":
+        return FusedAdam(arena, lr=args.base_lr, weight_decay=args.weight_decay)
+    if name == "adamw":
+        return FusedAdamW(arena, lr=args.base_lr, weight_decay=args.weight_decay)
+    return FusedSGD(arena, lr=args.base_lr, momentum=0.9, weight_decay=args.weight_decay)
+
+
+def get_scheduler(optimizer, args, max_iterations: int):
+    """core.py:27-40: args.scheduler in {'cosine', 'poly', 'exp', 'step', 'custom'} (any case); 'custom' reads args.base_lr and
+    args.max_epochs.  Step the result once per iteration after optimizer.step() (main_acdc.py:256-257)."""
+    name = args.scheduler.lower()
+    if name == "cosine":
+        return CosineLR(optimizer, T_max=max_iterations)
+    if name == "poly":
+        return PolyLR(optimizer, max_iterations=max_iterations)
+    if name == "exp":
+        return ExponentialLR(optimizer, gamma=0.95)
+    if name == "step":
+        return StepLR(optimizer, step_size=200, gamma=0.5)
+    if name == "custom":
+        return CustomLR(optimizer, T_first=5, lr_start_high=10 * args.base_lr, lr_end_high=5 * args.base_lr,
+                        lr_start_low=args.base_lr, lr_end_low=0, max_epochs=args.max_epochs)
+    raise NotImplementedError(f"Scheduler <{args.scheduler}> not implemented")
 
 
 def cenet_segments():

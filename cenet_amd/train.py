@@ -1,5 +1,5 @@
 """The reference's training loop (src/main_acdc.py:200-290) on the MI355X-native step: loader -> DevicePrefetcher -> STATIC input
-buffers -> one hipGraph replay per iteration (cenet_amd.graph.GraphedStep) -> poly learning rate -> per-epoch validation on the
+buffers -> one hipGraph replay per iteration (cenet_amd.graph.GraphedStep) -> learning-rate schedule -> per-epoch validation on the
 device (cenet_amd.evaluate.validate).
 
 What differs from the reference loop and why:
@@ -10,8 +10,8 @@ What differs from the reference loop and why:
     Dice sums depend on the batch, so it cannot be padded;
   * the loss is read back once per `log_every` iterations instead of every iteration (main_acdc.py:264-265: a device sync per
     step); the running epoch loss is accumulated on the device;
-  * the learning rate for the NEXT step is uploaded by FusedSGD.prepare() before each replay (no host value is baked into the
-    capture);
+  * the learning rate (and Adam's bias corrections) for the NEXT step is uploaded by the optimizer's prepare() before each
+    replay (no host value is baked into the capture);
   * the epoch log line prints the reference's quantity — the sum of the batch losses over the number of training images
     (main_acdc.py:264-267) — but accumulated on the device and read back once per epoch;
   * NOT here: the reference's `best.pth` / last-epoch checkpoint saves and its test inference after training
@@ -38,17 +38,23 @@ def _as_batches(loader) -> Iterable[dict]:
 def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, base_lr: float = 0.05, momentum: float = 0.9,
                weight_decay: float = 1e-4, loss_type: str = "dice,ce", loss_weights: str = "0.5,0.5", device="cuda:0",
                graph: bool = True, val_batches: Optional[Callable[[], Iterable]] = None, log_every: int = 20,
-               log: Callable[[str], None] = print) -> dict:
+               log: Callable[[str], None] = print, optimizer: str = "sgd", scheduler: str = "poly") -> dict:
     """main_acdc.py:200-290.  tr_loader yields {'image' [B,1,H,W] float, 'label' [B,H,W]} batches (host or device tensors);
     val_batches() yields (image [1,1,H,W], label [1,H,W]) pairs for the per-epoch validation (main_acdc.py:218-231).
+    optimizer / scheduler: the reference's --optimizer / --scheduler strings (main_acdc.py:34-35, core.py:12-41); `momentum`
+    applies to SGD, Adam / AdamW take betas (0.9, 0.999) and eps 1e-8 as the reference does.
     -> {'loss': per-iteration losses read back at log points, 'epoch_loss': [...], 'val_dice': [...], 'lr': [...]}"""
     from . import evaluate
     dev = torch.device(device)
     net = net.to(dev).train()
     crit = losses.Criterion(num_classes, argparse.Namespace(loss_type=loss_type, loss_weights=loss_weights))
     arena = optim.ParamArena(net, optim.cenet_segments())
-    opt = optim.FusedSGD(arena, lr=base_lr, momentum=momentum, weight_decay=weight_decay)
-    sched = optim.PolyLR(opt, max_iterations=max_epochs * len(tr_loader))
+    if optimizer.lower() == "sgd":
+        opt = optim.FusedSGD(arena, lr=base_lr, momentum=momentum, weight_decay=weight_decay)
+    else:
+        opt = optim.get_optimizer(net, argparse.Namespace(optimizer=optimizer, base_lr=base_lr, weight_decay=weight_decay))
+    sched = optim.get_scheduler(opt, argparse.Namespace(scheduler=scheduler, base_lr=base_lr, max_epochs=max_epochs),
+                                max_iterations=max_epochs * len(tr_loader))
     hist = {"loss": [], "epoch_loss": [], "val_dice": [], "lr": []}
     static = {}
     stepper: List[Optional[G.GraphedStep]] = [None]
@@ -68,11 +74,12 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
             static["lab"].copy_(lab, non_blocking=True)
             if stepper[0] is None:
                 # (the capture's warm-up runs are REAL optimizer steps: keep the model where it is with a snapshot)
-                snap = (arena.params.clone(), opt.buf.clone(), opt._steps,
+                snap = (arena.params.clone(), [b.clone() for b in opt.state_buffers()], opt._steps,
                         {k: v.clone() for k, v in net.state_dict().items() if "running_" in k or "num_batches" in k})
                 stepper[0] = G.GraphedStep(lambda: body(static["x"], static["lab"]), optimizer=opt, warmup=2)
                 arena.params.copy_(snap[0])
-                opt.buf.copy_(snap[1])
+                for b, saved in zip(opt.state_buffers(), snap[1]):
+                    b.copy_(saved)
                 opt._steps = snap[2]
                 net.load_state_dict(snap[3], strict=False)
                 arena.refresh_shadow()

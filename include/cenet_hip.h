@@ -532,6 +532,14 @@ int cenet_surface_border_u8(const unsigned char* mask, unsigned char* border, in
 int cenet_min_sqdist_i32(const int* a, int na, const int* b, int nb, int* out, cenet_stream_t stream);
 /* torch.optim.SGD(momentum, weight_decay) over a flat arena; hyper5 (device) = [lr, momentum, wd, grad_scale, first_step] */
 int cenet_sgd_step_f32(float* p, const float* g, float* buf, const float* hyper5, long n, cenet_stream_t stream);
+/* torch.optim.Adam / AdamW (amsgrad off) over a flat arena, one pass; exp_avg / exp_avg_sq are the flat fp32 moment buffers.
+ * hyper12 (device) = [lr, beta1, beta2, eps, wd, grad_scale, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t),
+ * decoupled (AdamW) flag, 1 - beta1, 1 - beta2, 1 - lr wd], the derived values computed on the host in double.  The _shadow form
+ * also rewrites the bf16 shadow of the parameters (as cenet_sgd_step_shadow_f32). */
+int cenet_adam_step_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, const float* hyper12, long n,
+                        cenet_stream_t stream);
+int cenet_adam_step_shadow_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, const float* hyper12, long n,
+                               unsigned short* shadow_bf16, cenet_stream_t stream);
 int cenet_zero_f32(float* p, long n, cenet_stream_t stream);
 /* zero-fill of any byte range (bf16 activations with an odd element count, views starting on an odd element): the buffers
  * torch.zeros / Tensor.zero_() would give the reference's autograd (e.g. the absent branch of a channel split) */
