@@ -117,6 +117,22 @@ __device__ __forceinline__ bf16x8 da_ld8(const bf* p, bool ok) {
   if (ok) memcpy(&f, p, 16);
   return f;
 }
+// hd = 4: the two heads of a pair share one 16-byte row (q_{2h} | q_{2h+1}); the chunk / fragment is loaded whole and half s is
+// kept in elements 0..3, elements 4..7 zeroed (the padding columns of the HDP = 16 tile)
+__device__ __forceinline__ void da_half(unsigned (&r)[4], int s) {
+  if (s) r[0] = r[2], r[1] = r[3];
+  r[2] = r[3] = 0u;
+}
+__device__ __forceinline__ bf16x8 da_ld4h(const bf* pair, int s, bool ok) {
+  unsigned u[4] = {0u, 0u, 0u, 0u};
+  if (ok) {
+    memcpy(u, pair, 16);
+    da_half(u, s);
+  }
+  bf16x8 f;
+  memcpy(&f, u, 16);
+  return f;
+}
 __device__ __forceinline__ bf16x8 da_pack8(const f32x16& x, int s) {  // registers 8s .. 8s+7 -> one B fragment
   unsigned u[4];
 #pragma unroll
@@ -161,7 +177,7 @@ struct DaGeo {
 // ONE: a single softmax over BOTH halves of the pair's 2*HDP query / key columns (one head of dimension 2*HDP = value width):
 // plain attention with head dimension 64 through the same tiles — the two half-products add into one score tile.  Tensors:
 // q, k, v [B, N, H*2HDP], U [B, H, N, 2HDP], lse / aug rows [B, H, N].
-template <int HDP, int QT, int MINB, bool ONE>
+template <int HDP, int QT, int MINB, bool ONE, bool H4 = false>
 __global__ __launch_bounds__(256, MINB) void dattn_fwd_kernel(DiffArgs a) {
   typedef DaGeo<HDP> G;
   constexpr int NKS = HDP / 16, NDT = G::DVP / 32, NH = ONE ? 1 : 2;
@@ -180,10 +196,12 @@ __global__ __launch_bounds__(256, MINB) void dattn_fwd_kernel(DiffArgs a) {
 
   // this thread's staged chunks (fixed for the whole key loop)
   DaChunk ch[CPT];
+  int hs[CPT];  // H4: which half of the staged 16-byte pair row the chunk keeps (-1: not a q / k chunk)
 #pragma unroll
   for (int j = 0; j < CPT; ++j) {
     const int id = tid + 256 * j;
     ch[j].fill = 0u;
+    hs[j] = -1;
     if (id >= NCH) {
       ch[j].g = nullptr;
       ch[j].lrow = 0;
@@ -192,7 +210,9 @@ __global__ __launch_bounds__(256, MINB) void dattn_fwd_kernel(DiffArgs a) {
       const int row = id / G::CK, cc = id - row * G::CK, s = cc / (HDP / 8), c8 = cc - s * (HDP / 8);
       ch[j].lrow = row;
       ch[j].loff = row * G::KP + s * HDP + 8 * c8;
-      ch[j].g = 8 * c8 < hd ? kb + (long)row * E + (2 * h + s) * hd + 8 * c8 : nullptr;
+      ch[j].g = H4 ? (c8 == 0 ? kb + (long)row * E + 2 * h * hd : nullptr)
+                   : (8 * c8 < hd ? kb + (long)row * E + (2 * h + s) * hd + 8 * c8 : nullptr);
+      hs[j] = s;
     } else {
       const int id2 = id - 32 * G::CK, row = id2 / G::CV, c8 = id2 - row * G::CV;
       ch[j].lrow = row;
@@ -203,8 +223,10 @@ __global__ __launch_bounds__(256, MINB) void dattn_fwd_kernel(DiffArgs a) {
   unsigned pre[CPT][4];
   auto fetch = [&](int k0) __attribute__((always_inline)) {
 #pragma unroll
-    for (int j = 0; j < CPT; ++j)
+    for (int j = 0; j < CPT; ++j) {
       da_fetch(ch[j], (long)k0 * (ch[j].loff < KIMG ? E : a.H * dv), N - k0, pre[j]);
+      if (H4 && hs[j] >= 0) da_half(pre[j], hs[j]);
+    }
   };
   auto stage = [&](int buf) __attribute__((always_inline)) {
 #pragma unroll
@@ -222,7 +244,8 @@ __global__ __launch_bounds__(256, MINB) void dattn_fwd_kernel(DiffArgs a) {
     for (int s = 0; s < 2; ++s) {
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks)
-        qf[t][s][ks] = da_ld8(qb + (long)qi * E + (2 * h + s) * hd + 16 * ks + 8 * hh, 16 * ks + 8 * hh < hd);
+        qf[t][s][ks] = H4 ? da_ld4h(qb + (long)qi * E + 2 * h * hd, s, hh == 0)
+                          : da_ld8(qb + (long)qi * E + (2 * h + s) * hd + 16 * ks + 8 * hh, 16 * ks + 8 * hh < hd);
     }
 #pragma unroll
     for (int s = 0; s < NH; ++s) {
@@ -348,7 +371,7 @@ __global__ __launch_bounds__(256, MINB) void dattn_fwd_kernel(DiffArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------------
 // (HDP <= 16: three workgroups per CU — 168 registers, nothing spilled; the kernel waits on dependent MFMA / exponential chains, a
 // third wave per SIMD covers more of them: 0.78 -> 0.74 ms at DSEB-56x56, same box)
-template <int HDP, bool ONE>
+template <int HDP, bool ONE, bool H4 = false>
 __global__ __launch_bounds__(256, HDP > 32 ? 1 : (HDP <= 16 ? 3 : 2)) void dattn_bwd_dq_kernel(DiffArgs a) {
   typedef DaGeo<HDP> G;
   constexpr int NKS = HDP / 16, NKD = G::DVP / 16, NH = ONE ? 1 : 2;
@@ -368,10 +391,12 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : (HDP <= 16 ? 3 : 2)) void dattn
   const int qi = q0 + r < N ? q0 + r : N - 1;
 
   DaChunk ch[CPT];
+  int hs[CPT];  // H4: which half of the staged 16-byte pair row the chunk keeps (-1: not a q / k chunk)
 #pragma unroll
   for (int j = 0; j < CPT; ++j) {
     const int id = tid + 256 * j;
     ch[j].fill = 0u;
+    hs[j] = -1;
     if (id >= NCH) {
       ch[j].g = nullptr;
       ch[j].lrow = 0;
@@ -380,7 +405,9 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : (HDP <= 16 ? 3 : 2)) void dattn
       const int row = id / G::CK, cc = id - row * G::CK, s = cc / (HDP / 8), c8 = cc - s * (HDP / 8);
       ch[j].lrow = row;
       ch[j].loff = row * G::KP + s * HDP + 8 * c8;
-      ch[j].g = 8 * c8 < hd ? kb + (long)row * E + (2 * h + s) * hd + 8 * c8 : nullptr;
+      ch[j].g = H4 ? (c8 == 0 ? kb + (long)row * E + 2 * h * hd : nullptr)
+                   : (8 * c8 < hd ? kb + (long)row * E + (2 * h + s) * hd + 8 * c8 : nullptr);
+      hs[j] = s;
     } else {
       const int id2 = id - 32 * G::CK, row = id2 / G::CV, c8 = id2 - row * G::CV;
       ch[j].lrow = row;
@@ -391,8 +418,10 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : (HDP <= 16 ? 3 : 2)) void dattn
   unsigned pre[CPT][4];
   auto fetch = [&](int k0) __attribute__((always_inline)) {
 #pragma unroll
-    for (int j = 0; j < CPT; ++j)
+    for (int j = 0; j < CPT; ++j) {
       da_fetch(ch[j], (long)k0 * (ch[j].loff < KIMG ? E : a.H * dv), N - k0, pre[j]);
+      if (H4 && hs[j] >= 0) da_half(pre[j], hs[j]);
+    }
   };
   auto stage = [&](int buf) __attribute__((always_inline)) {
 #pragma unroll
@@ -407,7 +436,8 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : (HDP <= 16 ? 3 : 2)) void dattn
   for (int s = 0; s < 2; ++s) {
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks)
-      qf[s][ks] = da_ld8(qb + (long)qi * E + (2 * h + s) * hd + 16 * ks + 8 * hh, 16 * ks + 8 * hh < hd);
+      qf[s][ks] = H4 ? da_ld4h(qb + (long)qi * E + 2 * h * hd, s, hh == 0)
+                     : da_ld8(qb + (long)qi * E + (2 * h + s) * hd + 16 * ks + 8 * hh, 16 * ks + 8 * hh < hd);
 #pragma unroll
     for (int ft = 0; ft < NFT; ++ft) dq[s][ft] = da_zero();
   }
@@ -513,7 +543,7 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : (HDP <= 16 ? 3 : 2)) void dattn
 // ---------------------------------------------------------------------------------------------------------------------------
 // backward, dK / dV: wave = 32 keys x both softmax heads (one shared dV accumulator); streams query tiles
 // ---------------------------------------------------------------------------------------------------------------------------
-template <int HDP, bool ONE>
+template <int HDP, bool ONE, bool H4 = false>
 __global__ __launch_bounds__(256, HDP > 32 ? 1 : 2) void dattn_bwd_dkv_kernel(DiffArgs a) {
   typedef DaGeo<HDP> G;
   constexpr int NKS = HDP / 16, NKD = G::DVP / 16, NDT = G::DVP / 32, NH = ONE ? 1 : 2;
@@ -536,10 +566,12 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : 2) void dattn_bwd_dkv_kernel(Di
 
   DaChunk ch[CPT];
   long gstep[CPT];  // elements per 32-row tile step of the chunk's tensor
+  int hs[CPT];      // H4: which half of the staged 16-byte pair row the chunk keeps (-1: not a q chunk)
 #pragma unroll
   for (int j = 0; j < CPT; ++j) {
     int id = tid + 256 * j;
     ch[j].fill = 0u;
+    hs[j] = -1;
     gstep[j] = 0;
     if (id >= NCH) {
       ch[j].g = nullptr;
@@ -549,7 +581,9 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : 2) void dattn_bwd_dkv_kernel(Di
       const int row = id / G::CK, cc = id - row * G::CK, s = cc / (HDP / 8), c8 = cc - s * (HDP / 8);
       ch[j].lrow = row;
       ch[j].loff = row * G::KP + s * HDP + 8 * c8;
-      ch[j].g = 8 * c8 < hd ? qb + (long)row * E + (2 * h + s) * hd + 8 * c8 : nullptr;
+      ch[j].g = H4 ? (c8 == 0 ? qb + (long)row * E + 2 * h * hd : nullptr)
+                   : (8 * c8 < hd ? qb + (long)row * E + (2 * h + s) * hd + 8 * c8 : nullptr);
+      hs[j] = s;
       gstep[j] = 32L * E;
     } else if ((id -= 32 * G::CK) < NH * 32 * G::CV) {  // dU rows of head s
       const int s = id / (32 * G::CV), id2 = id - s * 32 * G::CV, row = id2 / G::CV, c8 = id2 - row * G::CV;
@@ -570,7 +604,10 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : 2) void dattn_bwd_dkv_kernel(Di
   unsigned pre[CPT][4];
   auto fetch = [&](int q0) __attribute__((always_inline)) {
 #pragma unroll
-    for (int j = 0; j < CPT; ++j) da_fetch(ch[j], (q0 >> 5) * gstep[j], N - q0, pre[j]);
+    for (int j = 0; j < CPT; ++j) {
+      da_fetch(ch[j], (q0 >> 5) * gstep[j], N - q0, pre[j]);
+      if (H4 && hs[j] >= 0) da_half(pre[j], hs[j]);
+    }
   };
   auto stage = [&](int buf) __attribute__((always_inline)) {
 #pragma unroll
@@ -583,7 +620,8 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : 2) void dattn_bwd_dkv_kernel(Di
   for (int s = 0; s < 2; ++s)
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks)
-      kfB[s][ks] = da_ld8(kb + (long)ki * E + (2 * h + s) * hd + 16 * ks + 8 * hh, 16 * ks + 8 * hh < hd);
+      kfB[s][ks] = H4 ? da_ld4h(kb + (long)ki * E + 2 * h * hd, s, hh == 0)
+                      : da_ld8(kb + (long)ki * E + (2 * h + s) * hd + 16 * ks + 8 * hh, 16 * ks + 8 * hh < hd);
 #pragma unroll
   for (int kd = 0; kd < NKD; ++kd) vfB[kd] = da_ld8(vb + (long)ki * (a.H * dv) + 16 * kd + 8 * hh, 16 * kd + 8 * hh < dv);
   // constant B fragment of the statistics k-step: -1 at k = 0, 1, 2 (lane half 0), zero elsewhere
@@ -684,8 +722,19 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : 2) void dattn_bwd_dkv_kernel(Di
 }
 
 // head dims served: 8 and 16 (one k-step), 32 (two), 64 (four k-steps, two 32-feature accumulator tiles per head: the
-// 64x64-token level of the 512x512 three-scale preset, skin.sh:93-94)
-extern "C" int cenet_diffattn_heads_supported(int hd, int N) { return (hd == 8 || hd == 16 || hd == 32 || hd == 64) && N >= 1; }
+// 64x64-token level of the 512x512 three-scale preset, skin.sh:93-94); for skip_mode='add' (embed = C instead of 2C):
+// 4 (Synapse 56x56: the HDP = 16 tiles, the pair's two heads share one 16-byte row, H4) and 40 (ACDC 14x14: HDP = 48, three
+// k-steps and three 32-feature value tiles; the HDP = 64 tiles stay selectable for the A/B, da_hd40_p64).  Columns past hd are
+// zero in LDS and in the fragments, so scores and gradients are exact, and nothing is stored past the real columns.
+extern "C" int cenet_diffattn_heads_supported(int hd, int N) {
+  return (hd == 4 || hd == 8 || hd == 16 || hd == 32 || hd == 40 || hd == 64) && N >= 1;
+}
+// measurement aid (tools/skip_add_ab.py): hd = 40 through the HDP = 64 instances instead of HDP = 48; read per call so that one
+// process can time both
+static bool da_hd40_p64() {
+  const char* e = getenv("CENET_DATTN_HD40_HDP64");
+  return e && e[0] == '1';
+}
 extern "C" long cenet_diffattn_heads_ws_bytes(int B, int H, int N) { return (long)B * 2 * H * N * 16 * 2; }
 
 static int da_fill(DiffArgs& a, const cenet_diffattn_t* p) {
@@ -707,13 +756,17 @@ extern "C" int cenet_diffattn_heads_fwd_bf16(const cenet_diffattn_t* p, hipStrea
   const int rc = da_fill(a, p);
   if (rc != CENET_OK) return rc;
   const int bh = a.B * a.H;
-  if (a.hd <= 16) {
+  if (a.hd == 4) {
+    CENET_LAUNCH((dattn_fwd_kernel<16, 1, 3, false, true>), dim3(cdiv(a.N, 128), bh), dim3(256), stream, a);
+  } else if (a.hd <= 16) {
     // one 32-query tile per wave at three workgroups per CU (two tiles per wave need 256 registers and still spill)
     static const int v = getenv("CENET_DATTN_QT2") ? 2 : 1;
     if (v == 2 && a.N >= 1024) CENET_LAUNCH((dattn_fwd_kernel<16, 2, 2, false>), dim3(cdiv(a.N, 256), bh), dim3(256), stream, a);
     else CENET_LAUNCH((dattn_fwd_kernel<16, 1, 3, false>), dim3(cdiv(a.N, 128), bh), dim3(256), stream, a);
   } else if (a.hd <= 32) {
     CENET_LAUNCH((dattn_fwd_kernel<32, 1, 2, false>), dim3(cdiv(a.N, 128), bh), dim3(256), stream, a);
+  } else if (a.hd == 40 && !da_hd40_p64()) {
+    CENET_LAUNCH((dattn_fwd_kernel<48, 1, 1, false>), dim3(cdiv(a.N, 128), bh), dim3(256), stream, a);
   } else {
     CENET_LAUNCH((dattn_fwd_kernel<64, 1, 1, false>), dim3(cdiv(a.N, 128), bh), dim3(256), stream, a);
   }
@@ -727,12 +780,18 @@ extern "C" int cenet_diffattn_heads_bwd_bf16(const cenet_diffattn_t* p, hipStrea
   if (rc != CENET_OK) return rc;
   if (!a.dU || !a.dq || !a.dk || !a.dv || !a.aug) return CENET_EINVAL;
   const dim3 grid(cdiv(a.N, 128), a.B * a.H);
-  if (a.hd <= 16) {
+  if (a.hd == 4) {
+    CENET_LAUNCH((dattn_bwd_dq_kernel<16, false, true>), grid, dim3(256), stream, a);
+    CENET_LAUNCH((dattn_bwd_dkv_kernel<16, false, true>), grid, dim3(256), stream, a);
+  } else if (a.hd <= 16) {
     CENET_LAUNCH((dattn_bwd_dq_kernel<16, false>), grid, dim3(256), stream, a);
     CENET_LAUNCH((dattn_bwd_dkv_kernel<16, false>), grid, dim3(256), stream, a);
   } else if (a.hd <= 32) {
     CENET_LAUNCH((dattn_bwd_dq_kernel<32, false>), grid, dim3(256), stream, a);
     CENET_LAUNCH((dattn_bwd_dkv_kernel<32, false>), grid, dim3(256), stream, a);
+  } else if (a.hd == 40 && !da_hd40_p64()) {
+    CENET_LAUNCH((dattn_bwd_dq_kernel<48, false>), grid, dim3(256), stream, a);
+    CENET_LAUNCH((dattn_bwd_dkv_kernel<48, false>), grid, dim3(256), stream, a);
   } else {
     CENET_LAUNCH((dattn_bwd_dq_kernel<64, false>), grid, dim3(256), stream, a);
     CENET_LAUNCH((dattn_bwd_dkv_kernel<64, false>), grid, dim3(256), stream, a);

@@ -135,6 +135,59 @@ __global__ __launch_bounds__(256) void cat_channels_kernel(CatArgs<T> a) {
   }
 }
 
+// ---- add join of two equal-shape tensors (dseb.py:156, skip_mode='add': y = dec + skip) and its backward ----------------------
+// V = 16 / sizeof(T) elements per access over the first n - n % V elements (V = 1 when a pointer is not 16-byte aligned); the
+// last n % V elements are done by the first threads of the grid one by one.  bf16: upcast, add in fp32, round once (torch's add).
+template <typename T, int V>
+__global__ __launch_bounds__(256) void add2_fwd_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ y,
+                                                       long n) {
+  const long nv = n / V, i0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
+  for (long i = i0; i < nv; i += step) {
+    float u[V], w[V];
+    ldv<V>(u, a + i * V);
+    ldv<V>(w, b + i * V);
+#pragma unroll
+    for (int e = 0; e < V; ++e) u[e] += w[e];
+    stv<V>(y + i * V, u);
+  }
+  const long t = nv * V + i0;
+  if (t < n) stf(y + t, ldf(a + t) + ldf(b + t));
+}
+// da = g + ga, db = g + gb: g read once; ga / gb (nullptr: nothing) are the gradients that reached a / b by their other consumers
+template <typename T, int V>
+__global__ __launch_bounds__(256) void add2_bwd_kernel(const T* __restrict__ g, const T* __restrict__ ga, const T* __restrict__ gb,
+                                                       T* __restrict__ da, T* __restrict__ db, long n) {
+  const long nv = n / V, i0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
+  for (long i = i0; i < nv; i += step) {
+    float v[V], o[V];
+    ldv<V>(v, g + i * V);
+    if (ga) {
+      ldv<V>(o, ga + i * V);
+#pragma unroll
+      for (int e = 0; e < V; ++e) o[e] += v[e];
+      stv<V>(da + i * V, o);
+    } else {
+      stv<V>(da + i * V, v);
+    }
+    if (gb) {
+      ldv<V>(o, gb + i * V);
+#pragma unroll
+      for (int e = 0; e < V; ++e) o[e] += v[e];
+      stv<V>(db + i * V, o);
+    } else {
+      stv<V>(db + i * V, v);
+    }
+  }
+  const long t = nv * V + i0;
+  if (t < n) {
+    const float v = ldf(g + t);
+    if (ga) stf(da + t, ldf(ga + t) + v);
+    else da[t] = g[t];
+    if (gb) stf(db + t, ldf(gb + t) + v);
+    else db[t] = g[t];
+  }
+}
+
 // ---- space-to-depth of a token map: the kernel == stride spatial-reduction conv of pvtv2.py:93-95 reads each input
 // pixel exactly once, so gathering the s x s patches into rows turns it into a dense GEMM with both operands k-contiguous.
 // tok [B, Ho*S, Wo*S, C] <-> patch [B*Ho*Wo, C*S*S], k = (c, ky, kx) as in the conv weight [Cout, C, S, S].
@@ -1056,6 +1109,39 @@ static int split_channels_add_impl(T* p0, T* p1, T* p2, T* p3, const T* a0, cons
 CENET_TWIN(split_channels_add, (T* p0, T* p1, T* p2, T* p3, const T* a0, const T* a1, const T* a2, const T* a3, int c0, int c1,
                                 int c2, int c3, const T* joined, int B, long HW, hipStream_t stream),
            (p0, p1, p2, p3, a0, a1, a2, a3, c0, c1, c2, c3, joined, B, HW, stream))
+
+// grid for the add join: V-wide main part, at least one block (the scalar tail rides in its first threads)
+template <typename T>
+static dim3 add2_grid(long n, int V) {
+  long blocks = (n / V + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  return dim3((unsigned)(blocks > 0 ? blocks : 1));
+}
+template <typename T>
+static int add2_fwd_impl(const T* a, const T* b, T* y, long n, hipStream_t stream) {
+  if (!a || !b || !y || n <= 0) return CENET_EINVAL;
+  constexpr int VW = 16 / sizeof(T);
+  if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)y) & 15) == 0)
+    CENET_LAUNCH((add2_fwd_kernel<T, VW>), add2_grid<T>(n, VW), dim3(256), stream, a, b, y, n);
+  else
+    CENET_LAUNCH((add2_fwd_kernel<T, 1>), add2_grid<T>(n, 1), dim3(256), stream, a, b, y, n);
+  CENET_CHECK_LAUNCH();
+  return CENET_OK;
+}
+CENET_TWIN(add2_fwd, (const T* a, const T* b, T* y, long n, hipStream_t stream), (a, b, y, n, stream))
+template <typename T>
+static int add2_bwd_impl(const T* g, const T* ga, const T* gb, T* da, T* db, long n, hipStream_t stream) {
+  if (!g || !da || !db || n <= 0) return CENET_EINVAL;
+  constexpr int VW = 16 / sizeof(T);
+  if ((((uintptr_t)g | (uintptr_t)ga | (uintptr_t)gb | (uintptr_t)da | (uintptr_t)db) & 15) == 0)
+    CENET_LAUNCH((add2_bwd_kernel<T, VW>), add2_grid<T>(n, VW), dim3(256), stream, g, ga, gb, da, db, n);
+  else
+    CENET_LAUNCH((add2_bwd_kernel<T, 1>), add2_grid<T>(n, 1), dim3(256), stream, g, ga, gb, da, db, n);
+  CENET_CHECK_LAUNCH();
+  return CENET_OK;
+}
+CENET_TWIN(add2_bwd, (const T* g, const T* ga, const T* gb, T* da, T* db, long n, hipStream_t stream),
+           (g, ga, gb, da, db, n, stream))
 
 template <typename T>
 static int patch_tok_impl(const T* src, T* dst, int B, int Ho, int Wo, int C, int S, int inverse, hipStream_t stream) {

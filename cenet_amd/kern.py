@@ -852,6 +852,18 @@ def split_channels_add(parts, adds, joined, B, HW):
     _call("cenet_split_channels_add_f32", *ps, *ads, *cs, joined, B, L(HW))
 
 
+def add2_fwd(a, b, y, n):
+    """y = a + b over n elements (the add join of a DSEB in skip_mode='add'), one launch"""
+    _chk(a, b, y)
+    _call("cenet_add2_fwd_f32", a, b, y, L(n))
+
+
+def add2_bwd(g, ga, gb, da, db, n):
+    """da = g + ga, db = g + gb (ga / gb None: g alone) over n elements, one launch reading g once"""
+    _chk(g, da, db, *(t for t in (ga, gb) if t is not None))
+    _call("cenet_add2_bwd_f32", g, ga, gb, da, db, L(n))
+
+
 def im2col_tok(src, dst, B, H, W, C, K, stride, pad, inverse=False):
     _chk(src, dst)
     _call("cenet_im2col_tok_f32", src, dst, B, H, W, C, K, stride, pad, int(inverse))

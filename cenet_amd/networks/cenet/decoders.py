@@ -41,6 +41,6 @@ class Decoder(nn.Module):
             d = getattr(self, f"up{lvl}")(d)
             se = getattr(self, f"skip_enhancer{lvl}")
             e = se(s, d)
-            d, se.dec_tap = se.dec_tap, None  # (d itself, routed through the block's concat node: see DSEBlock.forward)
+            d, se.dec_tap = se.dec_tap, None  # (d itself, routed through the block's concat / add node: see DSEBlock.forward)
             d = getattr(self, f"dec{lvl}")(ops.add_act(d, e))
         return d

@@ -1,5 +1,5 @@
 """Dual Selective Enhancement Block on HIP kernels — mirrors reference src/networks/cenet/modules/dseb.py:26-165
-(use_command='dat-fea'; the 'dog' / 'seq' variants are not used by CENet)."""
+(use_command='dat-fea', mode 'cat' or 'add'; the 'dog' / 'seq' variants are not used by CENet)."""
 from __future__ import annotations
 
 import torch
@@ -42,10 +42,13 @@ class DSEBlock(nn.Module):
     def __init__(self, dim, scale_factors, num_heads, input_size, mode='add', use_command='dat-fea', depth=1, label="",
                  writer=None):
         super().__init__()
-        if mode.lower() != "cat" or use_command != "dat-fea":
-            raise NotImplementedError("CENet uses DSEBlock(mode='cat', use_command='dat-fea') only")
+        if use_command != "dat-fea":
+            raise NotImplementedError("CENet uses DSEBlock(use_command='dat-fea') only")
+        self.mode = mode.lower()
+        if self.mode not in ("cat", "add"):
+            raise ValueError(f"DSEBlock: mode must be 'cat' or 'add', got {mode!r}")
         self.input_size = input_size
-        _dim = dim * 2
+        _dim = dim * 2 if self.mode == "cat" else dim  # dseb.py:97
         self.boundary = FEA(dim=_dim, scale_factors=scale_factors, label=label, writer=writer)
         self.diffattn = MultiheadDiffAttn(embed_dim=_dim, depth=depth, num_heads=num_heads)
         self.mixer = nn.Conv2d(_dim, dim, kernel_size=1, stride=1, bias=False)
@@ -54,13 +57,16 @@ class DSEBlock(nn.Module):
     def forward(self, skip, dec):
         # dec has a second consumer in the decoder (decoders.py:96, the residual add).  It reads `self.dec_tap` (dec itself, routed
         # through the concat's autograd node) so that both of dec's gradients — and both of skip's — meet in the concat's backward
-        # kernel (ops.Concat2Fn) instead of two aten::add launches per level
-        y, dec, skip = ops.concat2(dec, skip, tap=True)
+        # kernel (ops.Concat2Fn; ops.Add2Fn for mode 'add', y = dec + skip) instead of two aten::add launches per level
+        if self.mode == "cat":
+            y, dec, skip = ops.concat2(dec, skip, tap=True)
+        else:
+            y, dec, skip = ops.add2(dec, skip, tap=True)
         self.dec_tap = dec
-        B, C2, H, W = y.shape
-        # dseb.py:115: the flat NCHW buffer re-read as [B, HW, 2C] tokens (a view, not a permute)
+        B, C2, H, W = y.shape  # (C2: 2C in mode 'cat', C in mode 'add')
+        # dseb.py:115: the flat NCHW buffer re-read as [B, HW, C2] tokens (a view, not a permute)
         # y has four consumers (the attention's projections, two down-samplings, the combine): each hands y on as a tap, so that the
-        # four gradients are added by the backward kernels along that chain instead of three aten::add launches on 2C-channel maps
+        # four gradients are added by the backward kernels along that chain instead of three aten::add launches on C2-channel maps
         diff, yt = self.diffattn(y.view(B, H * W, C2), None, None, True)
         rec, yt = self.boundary.recons(yt.view(B, C2, H, W), tap=True)
         z = ops.dseb_combine(yt, self.boundary.w, diff.view(B, C2, H, W), rec)  # (FEA(y)+y) + diff*y

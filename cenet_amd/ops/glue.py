@@ -93,6 +93,37 @@ def concat2(a, b, tap=False):
     return Concat2Fn.apply(a, b, tap)
 
 
+class Add2Fn(Function):
+    """dec + skip of equal shapes (dseb.py:156, skip_mode='add'): the add join, Concat2Fn's counterpart.
+    tap: also returns a and b themselves (a_tap, b_tap); the gradients their other consumers send through the taps are added by
+    the backward kernel, which writes da = g + ga and db = g + gb in one launch (no aten::add, no clone of g)."""
+
+    @staticmethod
+    def forward(ctx, a, b, tap=False):
+        a, b = _c(a), _c(b)
+        if a.shape != b.shape or a.dtype != b.dtype:
+            raise ValueError(f"add2: operands differ: {tuple(a.shape)} {a.dtype} vs {tuple(b.shape)} {b.dtype}")
+        y = _act(a.shape, a)
+        kern.add2_fwd(a, b, y, a.numel())
+        return (y, a.view_as(a), b.view_as(b)) if tap else y
+
+    @staticmethod
+    def backward(ctx, g, ga=None, gb=None):
+        if g is None:  # only the taps carried gradients
+            return ga, gb, None
+        g = _c(g)
+        ga = _c(ga) if ga is not None and ga.dtype == g.dtype else (None if ga is None else ga.to(g.dtype))
+        gb = _c(gb) if gb is not None and gb.dtype == g.dtype else (None if gb is None else gb.to(g.dtype))
+        da, db = _act(g.shape, g), _act(g.shape, g)
+        kern.add2_bwd(g, ga, gb, da, db, g.numel())
+        return da, db, None
+
+
+def add2(a, b, tap=True):
+    """a + b in one launch; tap=True returns (sum, a_tap, b_tap): hand the taps (not a / b) to the other consumers of a and b"""
+    return Add2Fn.apply(a, b, tap)
+
+
 class SplitChannelsFn(Function):
     """x[:, lo:hi] for consecutive channel groups of an NCHW tensor, as contiguous tensors (cfam.py:230)."""
 

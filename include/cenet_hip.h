@@ -460,6 +460,11 @@ int cenet_cat_channels_f32(float* p0, float* p1, float* p2, float* p3, int c0, i
 int cenet_split_channels_add_f32(float* p0, float* p1, float* p2, float* p3, const float* a0, const float* a1, const float* a2,
                                  const float* a3, int c0, int c1, int c2, int c3, const float* joined, int B, long HW,
                                  cenet_stream_t stream);
+/* Add join y = a + b of two equal-shape tensors (modules/dseb.py:156, skip_mode='add': `dec + skip`) and its backward:
+ * da = g + ga, db = g + gb in one launch that reads g once (ga / gb NULL: the copy alone).  ga / gb are the gradients that
+ * reached a / b through their other consumers (decoders.py:96's residual add, the mixer's `+ skip`). */
+int cenet_add2_fwd_f32(const float* a, const float* b, float* y, long n, cenet_stream_t stream);
+int cenet_add2_bwd_f32(const float* g, const float* ga, const float* gb, float* da, float* db, long n, cenet_stream_t stream);
 /* Space-to-depth of a token map for the kernel == stride spatial-reduction conv (reference networks/cenet/pvtv2.py:93-95,
  * `self.sr = nn.Conv2d(dim, dim, kernel_size=sr_ratio, stride=sr_ratio)` applied to x.permute(0,2,1).reshape(B,C,H,W)):
  * inverse == 0 gathers tok [B, Ho*S, Wo*S, C] into patch rows [B*Ho*Wo, C*S*S] (k = (c, ky, kx), the weight's own order);
@@ -582,6 +587,9 @@ int cenet_cat_channels_bf16(unsigned short* p0, unsigned short* p1, unsigned sho
 int cenet_split_channels_add_bf16(unsigned short* p0, unsigned short* p1, unsigned short* p2, unsigned short* p3,
     const unsigned short* a0, const unsigned short* a1, const unsigned short* a2, const unsigned short* a3, int c0, int c1, int c2,
     int c3, const unsigned short* joined, int B, long HW, cenet_stream_t stream);
+int cenet_add2_fwd_bf16(const unsigned short* a, const unsigned short* b, unsigned short* y, long n, cenet_stream_t stream);
+int cenet_add2_bwd_bf16(const unsigned short* g, const unsigned short* ga, const unsigned short* gb, unsigned short* da,
+    unsigned short* db, long n, cenet_stream_t stream);
 int cenet_patch_tok_bf16(const unsigned short* src, unsigned short* dst, int B, int Ho, int Wo, int C, int S, int inverse,
     cenet_stream_t stream);
 int cenet_im2col_tok_bf16(const unsigned short* src, unsigned short* dst, int B, int H, int W, int C, int K, int stride,
