@@ -33,13 +33,25 @@ struct AttnArgs {
   int q_dfast, k_dfast, v_dfast, o_dfast;  // 1: d is the contiguous dim (token layout); 0: token index contiguous (NCHW)
   int dv_atomic;
   float scale;
-  int finite_scores;  // forward: q pre-scaled, scores through nan_to_num (multihead_diffattn.py:95,106)
+  int finite_scores;  // q pre-scaled, scores through nan_to_num (multihead_diffattn.py:95,106); backward: dS = 0 where the raw
+                      // score was not finite (torch's nan_to_num backward is grad * isfinite(x))
 };
 
 // torch.nan_to_num on one fp32 score: NaN -> 0, +-inf -> +-FLT_MAX
 __device__ __forceinline__ float score_nan_to_num(float x) {
   if (x != x) return 0.f;
   return fminf(fmaxf(x, -3.402823466e+38f), 3.402823466e+38f);
+}
+__device__ __forceinline__ bool score_finite(float x) { return fabsf(x) <= 3.402823466e+38f; }  // false for NaN and +-inf
+
+// finite_scores: the reference scales q first (`q *= self.scaling`, multihead_diffattn.py:95), then multiplies — which products
+// overflow depends on it; each thread rescales exactly the elements stage_tile gave it (same index map), so no barrier is needed
+template <int DQ>
+__device__ __forceinline__ void prescale_staged_q(float* Qs, int pitch, int dfast, float scale) {
+  for (int idx = threadIdx.x; idx < 64 * DQ; idx += 256) {
+    const int r = dfast ? idx / DQ : idx & 63, c = dfast ? idx - (idx / DQ) * DQ : idx >> 6;
+    Qs[r * pitch + c] *= scale;
+  }
 }
 
 // stage a [64 x cols] tile (zero padded to colsp columns) into LDS dst[r*pitch + c]
@@ -84,7 +96,7 @@ struct TilePrefetch {
       r[j] = (row0 + rr < nrows && c < cols) ? src[(long)(row0 + rr) * s_row + (long)c * s_col] : 0.f;
     }
   }
-  __device__ __forceinline__ void store(float* dst, int pitch, int dfast) const {
+  __device__ __forceinline__ void store(float* dst, int pitch, int dfast, float mul = 1.f) const {
 #pragma unroll
     for (int j = 0; j < 64 * COLS / 256; ++j) {
       const int idx = threadIdx.x + 256 * j;
@@ -96,7 +108,7 @@ struct TilePrefetch {
         c = idx >> 6;
         rr = idx & 63;
       }
-      dst[rr * pitch + c] = r[j];
+      dst[rr * pitch + c] = r[j] * mul;
     }
   }
 };
@@ -148,15 +160,9 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(AttnArgs a) {
   const float* kb = a.k + (long)b * a.ksb + (long)h * a.ksh;
   const float* vb = a.v + (long)b * a.vsb + (long)hv * a.vsh;
   stage_tile(Qs, PQ, qb, a.qsi, a.qsd, i0, a.Nq, a.D, DQ, a.q_dfast);
-  // finite_scores: the reference scales q first (`q *= self.scaling`, multihead_diffattn.py:95), then multiplies — which products
-  // overflow depends on it; each thread rescales exactly the elements it staged (same index map as stage_tile)
   const bool fin = a.finite_scores != 0;
   const float lo = fin ? -3.402823466e+38f : NEG_BIG;  // below every nan_to_num'd score
-  if (fin)
-    for (int idx = threadIdx.x; idx < 64 * DQ; idx += 256) {
-      const int r = a.q_dfast ? idx / DQ : idx & 63, c = a.q_dfast ? idx - (idx / DQ) * DQ : idx >> 6;
-      Qs[r * PQ + c] *= a.scale;
-    }
+  if (fin) prescale_staged_q<DQ>(Qs, PQ, a.q_dfast, a.scale);
 
   f32x4 o[NV];
 #pragma unroll
@@ -263,6 +269,8 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(AttnArgs a) {
   const float* gb = a.dout + (long)b * a.osb + (long)h * a.osh;
   const int fr = lane & 15, fq = lane >> 4;
   stage_tile(Qs, PQ, qb, a.qsi, a.qsd, i0, a.Nq, a.D, DQ, a.q_dfast);
+  const bool fin = a.finite_scores != 0;  // scores rebuilt exactly as the forward made them
+  if (fin) prescale_staged_q<DQ>(Qs, PQ, a.q_dfast, a.scale);
   stage_tile(dOs, PV, gb, a.osi, a.osd, i0, a.Nq, a.Dv, DV, a.o_dfast);
   stage_tile(Vs, PV, ob, a.osi, a.osd, i0, a.Nq, a.Dv, DV, a.o_dfast);  // O staged temporarily in Vs
   __syncthreads();
@@ -309,8 +317,10 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(AttnArgs a) {
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float p = (j0 + 16 * t + fr < a.Nk) ? fast_exp(s[t][r] * a.scale - ls[r]) : 0.f;
+        const float raw = s[t][r];
+        float p = (j0 + 16 * t + fr < a.Nk) ? fast_exp((fin ? score_nan_to_num(raw) : raw * a.scale) - ls[r]) : 0.f;
         float ds = p * (dp[t][r] - dl[r]) * a.scale;
+        if (fin && !score_finite(raw)) ds = 0.f;
         Ps[(wave * 16 + fq * 4 + r) * PP + 16 * t + fr] = ds;
       }
     __syncthreads();
@@ -359,13 +369,16 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(AttnArgs a) {
 #pragma unroll
   for (int t = 0; t < NV; ++t) dv[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  // finite_scores: Q staged pre-scaled (scores as the forward made them); dS then carries no extra scale: dK = dS^T (scale Q)
+  const bool fin = a.finite_scores != 0;
+  const float qmul = fin ? a.scale : 1.f, dsmul = fin ? 1.f : a.scale;
   TilePrefetch<DQ> pq;
   TilePrefetch<DV> pg;
   pq.load(qb, a.qsi, a.qsd, 0, a.Nq, a.D, a.q_dfast);
   pg.load(gb, a.osi, a.osd, 0, a.Nq, a.Dv, a.o_dfast);
   for (int i0 = 0; i0 < a.Nq; i0 += TQ) {
     __syncthreads();
-    pq.store(Qs, PQ, a.q_dfast);
+    pq.store(Qs, PQ, a.q_dfast, qmul);
     pg.store(dOs, PV, a.o_dfast);
     if (threadIdx.x < TQ) {
       const int i = i0 + threadIdx.x;
@@ -394,8 +407,10 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(AttnArgs a) {
       for (int r = 0; r < 4; ++r) {
         const int jr = wave * 16 + fq * 4 + r;
         const bool ok = iv && (j0 + jr < a.Nk);
-        float p = ok ? fast_exp(st[t][r] * a.scale - lsev) : 0.f;
-        float ds = p * (dpt[t][r] - delv) * a.scale;
+        const float raw = st[t][r];
+        float p = ok ? fast_exp((fin ? score_nan_to_num(raw) : raw * a.scale) - lsev) : 0.f;
+        float ds = p * (dpt[t][r] - delv) * dsmul;
+        if (fin && !score_finite(raw)) ds = 0.f;
         Pt[jr * PP + ic] = p;
         St[jr * PP + ic] = ds;
       }
@@ -561,6 +576,41 @@ __global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const T* __restri
   for (int c = lane; c < n; c += 64) stf(dr + c, ldf(yr + c) * (gr[c] - s));
 }
 
+// finite_scores form of the two kernels above (fp32 parity mode, materialised path): the forward reads every score through
+// torch.nan_to_num (multihead_diffattn.py:106); the backward zeroes dx where the raw score s was not finite (nan_to_num's
+// backward is grad * isfinite(x))
+__global__ __launch_bounds__(256) void softmax_rows_finite_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long rows,
+                                                                     int n) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + wave;
+  if (row >= rows) return;
+  const float* xr = x + row * n;
+  float* yr = y + row * n;
+  float mx = -3.402823466e+38f;
+  for (int c = lane; c < n; c += 64) mx = fmaxf(mx, score_nan_to_num(xr[c]));
+  mx = wave_max(mx);
+  float s = 0.f;
+  for (int c = lane; c < n; c += 64) s += fast_exp(score_nan_to_num(xr[c]) - mx);
+  s = 1.f / wave_sum(s);
+  for (int c = lane; c < n; c += 64) yr[c] = fast_exp(score_nan_to_num(xr[c]) - mx) * s;
+}
+
+__global__ __launch_bounds__(256) void softmax_rows_finite_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy,
+                                                                     const float* __restrict__ x, float* __restrict__ dx,
+                                                                     long rows, int n) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + wave;
+  if (row >= rows) return;
+  const float* yr = y + row * n;
+  const float* gr = dy + row * n;
+  const float* xr = x + row * n;
+  float s = 0.f;
+  for (int c = lane; c < n; c += 64) s += yr[c] * gr[c];
+  s = wave_sum(s);
+  float* dr = dx + row * n;
+  for (int c = lane; c < n; c += 64) dr[c] = score_finite(xr[c]) ? yr[c] * (gr[c] - s) : 0.f;
+}
+
 template <typename T>
 static int softmax_rows_fwd_impl(const float* x, T* y, long rows, int n, hipStream_t stream) {
   if (rows <= 0 || n <= 0) return CENET_EINVAL;
@@ -577,3 +627,17 @@ static int softmax_rows_bwd_impl(const T* y, const float* dy, T* dx, long rows, 
   return CENET_OK;
 }
 CENET_TWIN(softmax_rows_bwd, (const T* y, const float* dy, T* dx, long rows, int n, hipStream_t stream), (y, dy, dx, rows, n, stream))
+
+extern "C" int cenet_softmax_rows_finite_fwd_f32(const float* x, float* y, long rows, int n, hipStream_t stream) {
+  if (!x || !y || rows <= 0 || n <= 0) return CENET_EINVAL;
+  CENET_LAUNCH(softmax_rows_finite_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, x, y, rows, n);
+  CENET_CHECK_LAUNCH();
+  return CENET_OK;
+}
+extern "C" int cenet_softmax_rows_finite_bwd_f32(const float* y, const float* dy, const float* x, float* dx, long rows, int n,
+                                                 hipStream_t stream) {
+  if (!y || !dy || !x || !dx || rows <= 0 || n <= 0) return CENET_EINVAL;
+  CENET_LAUNCH(softmax_rows_finite_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, y, dy, x, dx, rows, n);
+  CENET_CHECK_LAUNCH();
+  return CENET_OK;
+}

@@ -15,14 +15,15 @@
 //     32c+16+4fq of a [feature][row] (transposed) copy of the streamed tile;
 //   * the fixed side's own fragments (Q^T, dO^T or K^T, V^T) are loaded once from HBM into registers;
 //   * the streamed tiles are register-prefetched one tile ahead and double-buffered in LDS (one barrier per tile);
-//   * exponentials are v_exp_f32 (base 2): log2(e) is folded into the query scaling.
+//   * exponentials are v_exp_f32 (base 2): scale*log2(e) multiplies the fp32 scores (fused into the subtraction of the running
+//     max / LSE), never the bf16 operands: a query rounded to bf16 AFTER scaling would carry a relative 2^-9 error into every
+//     logit (|error| ~ 2^-9 |scale s|, a 4 % error of P at logits of 20; tests/test_attention_bounds.py).
 #include "common.h"
 #include "../../include/cenet_hip.h"
 
 #define TK 64
 #define NEG_BIG (-1.0e30f)
 #define LOG2E 1.4426950408889634f
-#define LN2 0.6931471805599453f
 #define PT 72  // pitch (elements) of [feature][64 rows] transposed tiles: 144-byte rows
 typedef unsigned short bf;
 
@@ -224,7 +225,8 @@ __global__ __launch_bounds__(256, (DV <= 64 ? 2 : 1)) void flashc_fwd_kernel(Att
   for (int t = 0; t < NQT; ++t)
 #pragma unroll
     for (int c = 0; c < NC; ++c)
-      qf[t][c] = frag_global(qb, a.qsi, a.qsd, q0 + 16 * t + fr, a.Nq, c, fq, a.D, a.scale * LOG2E, a.q_al);
+      qf[t][c] = frag_global(qb, a.qsi, a.qsd, q0 + 16 * t + fr, a.Nq, c, fq, a.D, 1.f, a.q_al);
+  const float c2 = a.scale * LOG2E;  // raw score -> base-2 logit
   f32x4 o[NQT][NU];
   float m[NQT], l[NQT];
 #pragma unroll
@@ -283,15 +285,16 @@ __global__ __launch_bounds__(256, (DV <= 64 ? 2 : 1)) void flashc_fwd_kernel(Att
 #pragma unroll
         for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[kt][t][r]);
       mx = quad_max(mx);
-      const float mnew = fmaxf(m[t], mx);
-      const float alpha = fast_exp2(m[t] - mnew);
+      const float mnew = fmaxf(m[t], mx);  // (raw scores: scale > 0, the maximum commutes with the scaling)
+      const float alpha = fast_exp2((m[t] - mnew) * c2);
       m[t] = mnew;
+      const float mc = mnew * c2;
       float rs = 0.f;
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float p = fast_exp2(st[kt][t][r] - mnew);
+          const float p = fast_exp2(fmaf(st[kt][t][r], c2, -mc));
           st[kt][t][r] = p;
           rs += p;
         }
@@ -333,7 +336,7 @@ __global__ __launch_bounds__(256, (DV <= 64 ? 2 : 1)) void flashc_fwd_kernel(Att
         for (int r = 0; r < 4; ++r) v[r] = o[t][u][r] * inv;
         put4(ob, a.osi, a.osd, i, 16 * u + 4 * fq, a.Dv, v, a.o_al, false);
       }
-      if (fq == 0) a.lse[((long)b * a.H + h) * a.Nq + i] = m[t] * LN2 + logf(lt);
+      if (fq == 0) a.lse[((long)b * a.H + h) * a.Nq + i] = m[t] * a.scale + logf(lt);
     }
   }
 }
@@ -364,7 +367,7 @@ __global__ __launch_bounds__(256, MINB) void flashc_bwd_dq_kernel(AttnArgsB a) {
   for (int t = 0; t < NQT; ++t) {
     const int i = q0 + 16 * t + fr;
 #pragma unroll
-    for (int c = 0; c < NC; ++c) qf[t][c] = frag_global(qb, a.qsi, a.qsd, i, a.Nq, c, fq, a.D, a.scale * LOG2E, a.q_al);
+    for (int c = 0; c < NC; ++c) qf[t][c] = frag_global(qb, a.qsi, a.qsd, i, a.Nq, c, fq, a.D, 1.f, a.q_al);
 #pragma unroll
     for (int c = 0; c < NCV; ++c) gf[t][c] = frag_global(gb, a.osi, a.osd, i, a.Nq, c, fq, a.Dv, 1.f, a.o_al);
     // delta = rowsum(dO * O) in fp32 from HBM: this lane's feature slots, then the 4 fq lanes
@@ -435,7 +438,7 @@ __global__ __launch_bounds__(256, MINB) void flashc_bwd_dq_kernel(AttnArgsB a) {
         for (int t = 0; t < NQT; ++t)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float p = fast_exp2(st[e][t][r] - lse2[t]);
+            const float p = fast_exp2(fmaf(st[e][t][r], a.scale * LOG2E, -lse2[t]));
             st[e][t][r] = p * (dp[e][t][r] - dl[t]);
           }
       }
@@ -478,7 +481,7 @@ template <int DQ, int DV, int NKT, int MINB>
 __global__ __launch_bounds__(256, MINB) void flashc_bwd_dkv_kernel(AttnArgsB a) {
   constexpr int PQ = DQ + 8, PV = DV + 8, NC = DQ / 32, NCV = DV / 32, ND = DQ / 16, NU = DV / 16;
   constexpr int NBUF = (DV <= 64) ? 2 : 1;  // the widest instance keeps one LDS stage (two barriers per tile)
-  __shared__ __attribute__((aligned(16))) bf Qs[NBUF][64 * PQ];   // [query][d]   (scaled by scale*log2e)
+  __shared__ __attribute__((aligned(16))) bf Qs[NBUF][64 * PQ];   // [query][d]
   __shared__ __attribute__((aligned(16))) bf Qt[NBUF][DQ * PT];   // [d][query]
   __shared__ __attribute__((aligned(16))) bf Gs[NBUF][64 * PV];   // dO [query][dv]
   __shared__ __attribute__((aligned(16))) bf Gt[NBUF][DV * PT];   // dO^T [dv][query]
@@ -526,7 +529,7 @@ __global__ __launch_bounds__(256, MINB) void flashc_bwd_dkv_kernel(AttnArgsB a) 
     }
   };
   auto store_tile = [&](int buf) __attribute__((always_inline)) {
-    sq.store(Qs[buf], PQ, Qt[buf], a.scale * LOG2E);
+    sq.store(Qs[buf], PQ, Qt[buf], 1.f);
     sg.store(Gs[buf], PV, Gt[buf], 1.f);
     if (threadIdx.x < 64) {
       lse_s[buf][threadIdx.x] = pl;
@@ -570,7 +573,7 @@ __global__ __launch_bounds__(256, MINB) void flashc_bwd_dkv_kernel(AttnArgsB a) 
           memcpy(d4, &del_s[cur][16 * qt + 4 * fq], 16);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float p = fast_exp2(s[e][r] - l4[r]);  // queries beyond the slice carry lse = +big -> p = 0
+            const float p = fast_exp2(fmaf(s[e][r], a.scale * LOG2E, -l4[r]));  // queries beyond the slice carry lse = +big -> p = 0
             s[e][r] = p;
             dp[e][r] = p * (dp[e][r] - d4[r]);
           }
@@ -600,7 +603,7 @@ __global__ __launch_bounds__(256, MINB) void flashc_bwd_dkv_kernel(AttnArgsB a) 
       for (int u = 0; u < ND; ++u) {
         float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = dk[t][u][r] * LN2;  // Q was staged scaled by scale*log2e
+        for (int r = 0; r < 4; ++r) v[r] = dk[t][u][r] * a.scale;
         if (a.dkv_f32) put4((float*)a.dk + dko, a.ksi, a.ksd, j, 16 * u + 4 * fq, a.D, v, a.k_al, split);
         else put4((bf*)a.dk + dko, a.ksi, a.ksd, j, 16 * u + 4 * fq, a.D, v, a.k_al, false);
       }

@@ -342,6 +342,18 @@ def softmax_rows_bwd(y, dy, dx, rows, n):
     _call("cenet_softmax_rows_bwd_f32", y, dy, dx, L(rows), n)
 
 
+def softmax_rows_finite_fwd(x, y, rows, n):
+    """fp32 parity mode: the scores x pass through torch.nan_to_num before the softmax (multihead_diffattn.py:106)"""
+    _chk(x, y)
+    _call("cenet_softmax_rows_finite_fwd_f32", x, y, L(rows), n)
+
+
+def softmax_rows_finite_bwd(y, dy, x, dx, rows, n):
+    """... and dx = 0 where the raw score x was not finite (nan_to_num's backward)"""
+    _chk(y, dy, x, dx)
+    _call("cenet_softmax_rows_finite_bwd_f32", y, dy, x, dx, L(rows), n)
+
+
 # ---- norms -----------------------------------------------------------------------------------------
 def layernorm_fwd(x, gamma, beta, y, mean, rstd, rows, Cn, eps):
     _chk(x, gamma, beta, y, mean, rstd)

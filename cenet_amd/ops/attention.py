@@ -27,7 +27,7 @@ class _AttnDesc:
         self.B, self.H, self.Nq, self.Nk, self.D, self.Dv, self.scale, self.vdiv = B, H, Nq, Nk, D, Dv, scale, vdiv
         self.qs, self.ks, self.vs, self.os = qs, ks, vs, os_  # each (sb, sh, si, sd)
         self.qoff, self.koff, self.voff = qoff, koff, voff   # element offsets into q/k/v storage
-        self.finite = False  # fp32 flash forward: q scaled first + torch.nan_to_num of the scores (multihead_diffattn.py:95,106)
+        self.finite = False  # fp32: q scaled first + torch.nan_to_num of the scores (multihead_diffattn.py:95,106), both directions
 
     def fill(self, a: "kern.AttnT", q, k, v, o, lse):
         e = kern.esz(q)
@@ -43,7 +43,7 @@ class _AttnDesc:
 
 
 def _attn_forward(d: _AttnDesc, q, k, v, o):
-    """returns the tensors to save for backward: ('flash', lse) or ('mat', P)."""
+    """returns the tensors to save for backward: ('flash', lse), ('mat', P) or, with d.finite, ('matf', [P, raw S])."""
     kern._chk(q, k, v, o)
     bf = _bf(q)
     if kern.flashb_supported(d.D, d.Dv) if bf else kern.flash_supported(d.D, d.Dv):
@@ -55,18 +55,31 @@ def _attn_forward(d: _AttnDesc, q, k, v, o):
     # materialised path (large head dims, small N): S = scale QK^T ; P = softmax ; O = P V.  The scores stay fp32 in both
     # modes (bf16 operands: the GEMM adds atomically into a zero-filled fp32 S); P has the operand type.
     BH = d.B * d.H
-    S = _empty((BH, d.Nq, d.Nk), q)  # (bf16 operands: the GEMM STORES its fp32 accumulators, atomic=2 — no zero fill)
-    kern.gemm(kern.mat_plain(q, d.qs[2], d.qs[3], sb=d.qs[0], sb2=d.qs[1], kfast=int(d.qs[3] == 1), offset=d.qoff),
+    fin = d.finite and not bf
+    if fin:
+        # parity mode (multihead_diffattn.py:95,106): q is scaled before the product, the scores go through nan_to_num; the
+        # raw scores are kept for the backward (dS = 0 where they were not finite).  Not benched: a scaled copy of q.
+        SP = torch.empty((2, BH, d.Nq, d.Nk), device=q.device, dtype=torch.float32)
+        S, P = SP[1], SP[0]
+        qa = torch.empty_like(q)
+        kern.scale_batch(q, torch.full((1,), d.scale, device=q.device), qa, 1, q.numel())
+    else:
+        S = _empty((BH, d.Nq, d.Nk), q)  # (bf16 operands: the GEMM STORES its fp32 accumulators, atomic=2 — no zero fill)
+        qa = q
+    kern.gemm(kern.mat_plain(qa, d.qs[2], d.qs[3], sb=d.qs[0], sb2=d.qs[1], kfast=int(d.qs[3] == 1), offset=d.qoff),
               kern.mat_plain(k, d.ks[3], d.ks[2], sb=d.ks[0], sb2=d.ks[1], kfast=int(d.ks[3] == 1), offset=d.koff),
               S, d.Nq, d.Nk, d.D, scr=d.Nk, scc=1, scb=d.H * d.Nq * d.Nk, scb2=d.Nq * d.Nk, nbatch=BH, nb_inner=d.H,
-              alpha=d.scale, atomic=2 if bf else False)
-    P = _act(S.shape, q)
-    kern.softmax_rows_fwd(S, P, BH * d.Nq, d.Nk)
+              alpha=1.0 if fin else d.scale, atomic=2 if bf else False)
+    if fin:
+        kern.softmax_rows_finite_fwd(S, P, BH * d.Nq, d.Nk)
+    else:
+        P = _act(S.shape, q)
+        kern.softmax_rows_fwd(S, P, BH * d.Nq, d.Nk)
     vh = d.vdiv
     kern.gemm(kern.mat_plain(P, d.Nk, 1, sb=d.H * d.Nq * d.Nk, sb2=d.Nq * d.Nk, kfast=1),
               _vmat(d, v, vh), o, d.Nq, d.Dv, d.Nk, scr=d.os[2], scc=d.os[3], scb=d.os[0], scb2=d.os[1], nbatch=BH,
               nb_inner=d.H)
-    return "mat", P
+    return ("matf", SP) if fin else ("mat", P)
 
 
 def _vmat(d: _AttnDesc, v, vh):
@@ -93,7 +106,7 @@ def _attn_backward(d: _AttnDesc, kind, saved, q, k, v, o, g, dq, dk, dv, dkv_zer
         a.delta = delta.data_ptr()
         kern.flash_bwd(a, bf)
         return
-    P = saved
+    P, S = (saved[0], saved[1]) if kind == "matf" else (saved, None)
     BH = d.B * d.H
     HN = d.H * d.Nq * d.Nk
     NN = d.Nq * d.Nk
@@ -102,7 +115,10 @@ def _attn_backward(d: _AttnDesc, kind, saved, q, k, v, o, g, dq, dk, dv, dkv_zer
               kern.mat_plain(v, d.vs[3], d.vs[2], sb=d.vs[0], sb2=d.vs[1], kfast=int(d.vs[3] == 1), offset=d.voff),
               dP, d.Nq, d.Nk, d.Dv, scr=d.Nk, scc=1, scb=HN, scb2=NN, nbatch=BH, nb_inner=d.H, atomic=2 if bf else False)
     dS = torch.empty_like(P)
-    kern.softmax_rows_bwd(P, dP, dS, BH * d.Nq, d.Nk)
+    if S is not None:
+        kern.softmax_rows_finite_bwd(P, dP, S, dS, BH * d.Nq, d.Nk)
+    else:
+        kern.softmax_rows_bwd(P, dP, dS, BH * d.Nq, d.Nk)
     kern.gemm(kern.mat_plain(dS, d.Nk, 1, sb=HN, sb2=NN, kfast=1),
               kern.mat_plain(k, d.ks[2], d.ks[3], sb=d.ks[0], sb2=d.ks[1], kfast=int(d.ks[2] == 1), offset=d.koff),
               dq, d.Nq, d.D, d.Nk, scr=d.qs[2], scc=d.qs[3], scb=d.qs[0], scb2=d.qs[1], nbatch=BH, nb_inner=d.H,
@@ -267,6 +283,7 @@ class DiffAttnHeadsFn(Function):
             for s in (0, 1):
                 d = _AttnDesc(B, H, N, N, hd, dv, hd ** -0.5, 1, (N * E, 2 * hd, E, 1), (N * E, 2 * hd, E, 1),
                               (N * E, dv, E, 1), (2 * H * N * dv, 2 * N * dv, dv, 1), qoff=s * hd, koff=s * hd)
+                d.finite = not _bf(q)  # (as above: parity mode only)
                 Us = U  # written through an offset view
                 kind, saved = _attn_forward(d, q, k, v, _OffsetView(Us, s * N * dv))
                 ctx.descs.append(d)

@@ -173,10 +173,11 @@ typedef struct {
   int dkv_zeroed; /* backward only: caller guarantees dk / dv are zero-filled, so the library may slice the query range
                      over workgroups and accumulate dK / dV atomically (few keys under many queries) */
   int dkv_f32;    /* bf16 entry points only: dk / dv are fp32 accumulators */
-  int finite_scores; /* cenet_flash_attn_fwd_f32 only (multihead_diffattn.py:95-106): q is scaled BEFORE the product (`q *= self.scaling`)
+  int finite_scores; /* fp32 entry points only (multihead_diffattn.py:95-106): q is scaled BEFORE the product (`q *= self.scaling`)
                         and the scores pass through torch.nan_to_num (NaN -> 0, +-inf -> +-FLT_MAX) before the softmax, so a q.k
-                        product that overflows fp32 gives the reference's finite output.  The bf16 entry points and the backward
-                        ignore it (overflowing scores are outside the supported domain there: INTEGRATION.md) */
+                        product that overflows fp32 gives the reference's finite output; the backward rebuilds the scores the
+                        same way and sets dS = 0 where the raw score was not finite (nan_to_num's backward).  The bf16 entry
+                        points ignore it (overflowing scores are outside the supported domain there: INTEGRATION.md) */
 } cenet_attn_t;
 /* Replaces q@k^T -> softmax -> @v (pvtv2.py:101-105; nlb.py:117-138; multihead_diffattn.py:96-116) and backward.
  * Supported head dims: D<=64 with Dv<=128 (cenet_flash_attn_supported). */
@@ -241,6 +242,12 @@ int cenet_softmax_rows_bwd_f32(const float* y, const float* dy, float* dx, long 
 int cenet_softmax_rows_fwd_bf16(const float* x, unsigned short* y, long rows, int n, cenet_stream_t stream);
 int cenet_softmax_rows_bwd_bf16(const unsigned short* y, const float* dy, unsigned short* dx, long rows, int n,
                                 cenet_stream_t stream);
+/* fp32 parity mode with non-finite scores (cenet_attn_t.finite_scores on the materialised path, multihead_diffattn.py:106): the
+ * forward reads every score x through torch.nan_to_num; the backward takes the raw scores x as well and writes dx = 0 wherever
+ * x is not finite (nan_to_num's backward is grad * isfinite(x)). */
+int cenet_softmax_rows_finite_fwd_f32(const float* x, float* y, long rows, int n, cenet_stream_t stream);
+int cenet_softmax_rows_finite_bwd_f32(const float* y, const float* dy, const float* x, float* dx, long rows, int n,
+                                      cenet_stream_t stream);
 
 /* ---- normalisation (norm.hip) ----------------------------------------------------------------------------- */
 /* aten::native_layer_norm(+_backward) — pvtv2.py:117,124,166,69,221-245. x,y [rows,C]. */

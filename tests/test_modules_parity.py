@@ -101,6 +101,23 @@ def test_nonfinite_scores_follow_the_reference_in_parity_mode(dev):
         out = m(x)
     assert torch.isfinite(out).all()
     close(out, z["out_eval"], what="out_eval (non-finite scores)")
+    # backward (parity mode applies nan_to_num in both directions, torch's nan_to_num backward is grad * isfinite(scores)): where
+    # the reference formula's input gradient under autograd is finite, so is the product's.  (Values are not compared: with
+    # weights of 1e19 the rows are one-hot, where the reference's softmax backward cancels exactly and delta = rowsum(dO O) leaves a
+    # rounding residual that the weights amplify; tests/test_attention_bounds.py compares values on well-conditioned overflow.)
+    from oracle import cenet_oracle as O
+    sdr = {"m." + k: v.detach().cpu() for k, v in sd.items()}
+    xr = x.detach().cpu().clone().requires_grad_(True)
+    yr = O.multihead_diff_attn(sdr, "m", xr, 2, 2)
+    cot = torch.randn(yr.shape, generator=torch.Generator().manual_seed(7))
+    yr.backward(cot)
+    assert torch.isfinite(xr.grad).all()
+    xt = x.detach().clone().requires_grad_(True)
+    m.train()
+    yt = m(xt)
+    assert torch.isfinite(yt).all()
+    yt.backward(cot.to(dev))
+    assert torch.isfinite(xt.grad).all()
     old = kern.set_compute_bf16(True)
     try:
         with torch.no_grad():
