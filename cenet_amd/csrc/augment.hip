@@ -17,12 +17,10 @@
 // and images agree to the last float32 bit in practice (tests/test_augment.py holds them to 1e-6 and counts exact matches).
 #include "common.h"
 #include "../../include/cenet_hip.h"
-
-#pragma clang fp contract(off)
+#include "spline3.h"  // aug_prefilter_line, aug_w3, aug_mirror, aug_cubic_at; fp contraction off from here on
 
 #define AUG_TAB 8   // per sample: offset (elements into the pools), H, W, mode, k, axis, zoom flag, unused
 #define AUG_DP 10   // per sample: m00 m01 m10 m11 off0 off1 | pole^(Ha-1) pole^(Wa-1) | zoom_y zoom_x
-#define AUG_POLE (-0.26794919243112270647)  // sqrt(3) - 2
 
 __device__ __forceinline__ void aug_staged_size(const long* t, int& Ha, int& Wa) {
   const int H = (int)t[1], W = (int)t[2];
@@ -79,24 +77,6 @@ __global__ __launch_bounds__(256) void aug_geom_kernel(const float* __restrict__
   }
 }
 
-// one line of scipy's spline_filter1d(order=3), mirror boundary: c[0 .. n) at stride s, zn = pole^(n-1)
-__device__ __forceinline__ void aug_prefilter_line(double* c, int n, long s, double zn) {
-  if (n < 2) return;
-  const double z = AUG_POLE;
-  const double gain = (1.0 - z) * (1.0 - 1.0 / z);
-  for (int i = 0; i < n; ++i) c[i * s] *= gain;
-  double zi = z;
-  double c0 = c[0] + zn * c[(n - 1) * s];
-  for (int i = 1; i < n - 1; ++i) {
-    c0 += (zi + zn * zn / zi) * c[i * s];
-    zi *= z;
-  }
-  c[0] = c0 / (1.0 - zn * zn);
-  for (int i = 1; i < n; ++i) c[i * s] += z * c[(i - 1) * s];
-  c[(n - 1) * s] = (z * c[(n - 2) * s] + c[(n - 1) * s]) * z / (z * z - 1.0);
-  for (int i = n - 2; i >= 0; --i) c[i * s] = z * (c[(i + 1) * s] - c[i * s]);
-}
-
 // AXIS 0: thread = one column (lines run down the rows, neighbouring threads read neighbouring addresses); AXIS 1: thread = one
 // row.  grid (chunks of lines, B).  Samples that are not resized skip the filter.
 template <int AXIS>
@@ -114,26 +94,6 @@ __global__ __launch_bounds__(64) void aug_prefilter_kernel(const long* __restric
   } else {
     if (line < Ha) aug_prefilter_line(c + (long)line * Wa, Wa, 1, dp[(long)b * AUG_DP + 7]);
   }
-}
-
-__device__ __forceinline__ void aug_w3(double t, double* w) {  // cubic B-spline weights of the taps floor - 1 .. floor + 2
-  w[1] = (t * t * (t - 2.0) * 3.0 + 4.0) / 6.0;
-  const double z = 1.0 - t;
-  w[2] = (z * z * (z - 2.0) * 3.0 + 4.0) / 6.0;
-  w[0] = z * z * z / 6.0;
-  w[3] = 1.0 - w[0] - w[1] - w[2];
-}
-__device__ __forceinline__ int aug_mirror(int idx, int n) {  // scipy NI_ZoomShift tap mapping (all non-grid modes)
-  if (n <= 1) return 0;
-  const int s2 = 2 * n - 2;
-  if (idx < 0) {
-    idx = s2 * (-idx / s2) + idx;
-    idx = idx <= 1 - n ? idx + s2 : -idx;
-  } else if (idx >= n) {
-    idx -= s2 * (idx / s2);
-    if (idx >= n) idx = s2 - idx;
-  }
-  return idx;
 }
 
 // grid (chunks, B)
@@ -165,22 +125,7 @@ __global__ __launch_bounds__(256) void aug_zoom_kernel(const long* __restrict__ 
       ol[p] = 0.f;
       continue;
     }
-    const int fy = (int)floor(cy), fx = (int)floor(cx);
-    double wy[4], wx[4];
-    aug_w3(cy - (double)fy, wy);
-    aug_w3(cx - (double)fx, wx);
-    int yy[4], xx[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      yy[a] = aug_mirror(fy - 1 + a, Ha);
-      xx[a] = aug_mirror(fx - 1 + a, Wa);
-    }
-    double acc = 0.0;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc += c[(long)yy[a] * Wa + xx[e]] * wy[a] * wx[e];
-    oi[p] = (float)acc;
+    oi[p] = (float)aug_cubic_at(c, Ha, Wa, cy, cx);
     ol[p] = (float)l[(long)(int)floor(cy + 0.5) * Wa + (int)floor(cx + 0.5)];
   }
 }

@@ -14,7 +14,10 @@ produces the masks and the overlap counts (loss_optim.hip).
     to the other border) run on the device in exact integer arithmetic (metrics.hip); only the final percentile / mean of
     the few thousand distances is taken on the host, in float64 like numpy does.
 The scipy cubic `zoom` of slices that do not have the network's input size is the reference's own host-side dependency
-(metrics_eval.py:45,55) and is called the same way here.
+(metrics_eval.py:45,55); `resize="host"` (the default) calls it the same way, `resize="device"` runs both resizes on the device
+(csrc/volresize.hip through `predict_volume`: the volume is uploaded once and only the metric numbers come back).
+  * `val_single_volume` (metrics_eval.py:87-122) and `inference` (utils_acdc.py:7-33) — the per-epoch test run of
+    main_acdc.py:270-289 and `--eval`.
 """
 from __future__ import annotations
 
@@ -155,19 +158,116 @@ def metric_percase(pred: torch.Tensor, gt: torch.Tensor) -> Tuple[float, float, 
     return 0, 0, 0, 0
 
 
+def _device_case(image, label, device, patch_size):
+    """image and label [D, H, W] on the device (one upload each), or None when the device resize does not take the case: a 2-D
+    input, or an axis of length 1 that has to be resized (scipy special-cases those; the host path handles them)"""
+    image = image.squeeze(0) if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))
+    label = label.squeeze(0) if torch.is_tensor(label) else torch.from_numpy(np.ascontiguousarray(label))
+    if image.dim() != 3:
+        return None
+    H, W = image.shape[1:]
+    PH, PW = int(patch_size[0]), int(patch_size[1])
+    if (H, W) != (PH, PW) and not kern.vol_resize_supported(H, W, PH, PW):
+        return None
+    return image.to(device), label.to(device)
+
+
+def _predict_volume_host(net, image: np.ndarray, label: np.ndarray, patch_size, batch_slices, device) -> np.ndarray:
+    """the prediction loop of val_single_volume with the reference's host resizes (the loop `test_single_volume` runs)"""
+    from scipy.ndimage import zoom
+    D, x, y = image.shape
+    resize = (x != patch_size[0] or y != patch_size[1])
+    prediction = np.zeros_like(label)
+    for s in range(0, D, batch_slices):
+        sl = image[s:s + batch_slices]
+        if resize:
+            sl = np.stack([zoom(a, (patch_size[0] / x, patch_size[1] / y), order=3) for a in sl])
+        inp = torch.from_numpy(np.ascontiguousarray(sl)).unsqueeze(1).float().to(device)
+        with ops.batch1_semantics():
+            logits = net(inp)
+        pred, _ = predict_counts(logits)
+        out = pred.reshape(-1, patch_size[0], patch_size[1]).cpu().numpy()
+        for i in range(out.shape[0]):
+            prediction[s + i] = zoom(out[i], (x / patch_size[0], y / patch_size[1]), order=0) if resize else out[i]
+    return prediction
+
+
+def _save_case(test_save_path, case, z_spacing, prediction, image, label):
+    """the reference writes NIfTI files through SimpleITK (absent here): .npy volumes and the spacing in a side-car text file"""
+    import os
+    os.makedirs(test_save_path, exist_ok=True)
+    for tag, vol in (("pred", prediction), ("img", image), ("gt", label)):
+        vol = vol.cpu().numpy() if torch.is_tensor(vol) else vol
+        np.save(os.path.join(test_save_path, f"{case}_{tag}.npy"), np.asarray(vol, dtype=np.float32))
+    with open(os.path.join(test_save_path, f"{case}_spacing.txt"), "w") as f:
+        f.write(f"1 1 {z_spacing}\n")
+
+
+@torch.no_grad()
+def predict_volume(net, volume: torch.Tensor, patch_size: Sequence[int], batch_slices: int = 32, normalize=None,
+                   labels: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The prediction loop of test_single_volume (metrics_eval.py:41-58, utils_synapse.py:53-76) without leaving the device:
+    volume [D, H, W] on the device -> (prediction [D, H, W] class ids as float, counts [K + 1, 3] int64 over the whole volume
+    when `labels` [D, H, W] is given, else None).  Per chunk of `batch_slices` slices: zoom(order=3) to `patch_size` (skipped when
+    the slices already have it, as the reference does), optional `normalize = (mean, std)`, forward with the reference's batch-1
+    semantics, argmax + zoom(order=0) back in one kernel.  H, W and the patch sides must be >= 2 when they differ."""
+    assert volume.dim() == 3, "volume [D,H,W] expected"
+    D, H, W = volume.shape
+    PH, PW = int(patch_size[0]), int(patch_size[1])
+    resize = (H != PH or W != PW)
+    if resize and not kern.vol_resize_supported(H, W, PH, PW):
+        raise ValueError(f"the device resize needs sides >= 2, got {(H, W)} -> {(PH, PW)}")
+    volume = volume.float().contiguous()
+    pred = torch.empty((D, H, W), device=volume.device, dtype=torch.float32)
+    total = None
+    if labels is not None:
+        labels = labels.reshape(D, H, W).float().contiguous()
+    stage = torch.empty(min(D, batch_slices) * H * W, device=volume.device, dtype=torch.float64) if resize else None
+    for s in range(0, D, batch_slices):
+        sl = volume[s:s + batch_slices]
+        n = sl.shape[0]
+        if resize:
+            inp = torch.empty((n, 1, PH, PW), device=volume.device, dtype=torch.float32)
+            kern.vol_resize_cubic(sl, stage, inp, n, H, W, PH, PW, normalize)
+        else:
+            inp = sl.unsqueeze(1)
+            if normalize is not None:
+                inp = (inp - normalize[0]) / normalize[1]
+        with ops.batch1_semantics():  # slice-by-slice semantics of the reference (CCU's `if B > 1` BatchNorm, cfam.py:260)
+            logits = net(inp).contiguous()
+        K = logits.shape[1]
+        counts = None
+        if labels is not None:
+            counts = torch.empty((K + 1, 3), device=volume.device, dtype=torch.int32)
+        kern.argmax_resize_counts(logits, None if labels is None else labels[s:s + n], pred[s:s + n], counts, n, K, PH, PW, H, W)
+        if counts is not None:
+            total = counts.long() if total is None else total + counts.long()
+    return pred, total
+
+
 @torch.no_grad()
 def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int] = (224, 224), batch_slices: int = 32,
-                       device=None) -> List[Tuple[float, float, float, float]]:
+                       device=None, resize: str = "host", test_save_path=None, case=None,
+                       z_spacing: float = 1.0) -> List[Tuple[float, float, float, float]]:
     """test_single_volume (metrics_eval.py:37-84) for a 3-D volume: image / label [1,D,H,W] or [D,H,W] (tensor or ndarray).
     Slices are resized to `patch_size` with scipy's cubic zoom and the predictions back with order 0 exactly as the
     reference does (host side), but the network runs on batches of slices and the metrics on the device.
+    `resize="device"`: image and label are uploaded once and both resizes run on the device (`predict_volume`); a case the
+    device resize does not take (an axis of length 1) goes the host way.  `test_save_path`: see `_save_case`.
     Returns [(dice, hd95, jaccard, assd)] for classes 1..classes-1."""
     from scipy.ndimage import zoom
+    assert resize in ("host", "device"), resize
+    device = device or next(net.parameters()).device
+    net.eval()
+    on_dev = _device_case(image, label, device, patch_size) if resize == "device" else None
+    if on_dev is not None:
+        pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices)
+        if test_save_path is not None:
+            _save_case(test_save_path, case, z_spacing, pred_d, on_dev[0], on_dev[1])
+        return [metric_percase(pred_d == c, on_dev[1] == c) for c in range(1, classes)]
     image = image.squeeze(0).cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
     label = label.squeeze(0).cpu().numpy() if torch.is_tensor(label) else np.asarray(label)
     assert image.ndim == 3, "volume [D,H,W] expected"
-    device = device or next(net.parameters()).device
-    net.eval()
     D, x, y = image.shape
     resize = (x != patch_size[0] or y != patch_size[1])
     prediction = np.zeros_like(label)
@@ -184,6 +284,8 @@ def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int
             prediction[s + i] = zoom(out[i], (x / patch_size[0], y / patch_size[1]), order=0) if resize else out[i]
     pred_d = torch.from_numpy(np.ascontiguousarray(prediction)).to(device)
     lab_d = torch.from_numpy(np.ascontiguousarray(label)).to(device)
+    if test_save_path is not None:
+        _save_case(test_save_path, case, z_spacing, prediction, image, label)
     return [metric_percase(pred_d == c, lab_d == c) for c in range(1, classes)]
 
 
@@ -206,18 +308,26 @@ def synapse_metric_percase(pred: torch.Tensor, gt: torch.Tensor) -> Tuple[float,
 
 @torch.no_grad()
 def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequence[int] = (256, 256), test_save_path=None,
-                               case=None, z_spacing: float = 1.0, batch_slices: int = 32, device=None):
+                               case=None, z_spacing: float = 1.0, batch_slices: int = 32, device=None, resize: str = "host"):
     """test_single_volume of utils_synapse.py:49-97: every slice of the volume [1, D, H, W] is resized to `patch_size` (cubic
     zoom), normalised with Normalize([0.5], [0.5]) (`ToTensor` leaves float arrays unscaled), classified, and the prediction
     resized back with order 0; returns [(dice, hd95)] for classes 1..classes-1.  A 2-D input takes the reference's second branch
     (one forward, no normalisation).  The slices go through the network in batches (with the reference's batch-1 semantics),
     the metrics run on the device.  `test_save_path` (NIfTI files through SimpleITK, which is absent here) writes .npy volumes
-    with the spacing (1, 1, z_spacing) in a side-car text file instead."""
+    with the spacing (1, 1, z_spacing) in a side-car text file instead.  `resize="device"`: as for `test_single_volume`, with the
+    normalisation inside the resize kernel; the 2-D branch has no resize and is the same in both modes."""
     from scipy.ndimage import zoom
-    image = image.squeeze(0).cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
-    label = label.squeeze(0).cpu().numpy() if torch.is_tensor(label) else np.asarray(label)
+    assert resize in ("host", "device"), resize
     device = device or next(net.parameters()).device
     net.eval()
+    on_dev = _device_case(image, label, device, patch_size) if resize == "device" else None
+    if on_dev is not None:
+        pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices, normalize=(0.5, 0.5))
+        if test_save_path is not None:
+            _save_case(test_save_path, case, z_spacing, pred_d, on_dev[0], on_dev[1])
+        return [synapse_metric_percase(pred_d == c, on_dev[1] == c) for c in range(1, classes)]
+    image = image.squeeze(0).cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
+    label = label.squeeze(0).cpu().numpy() if torch.is_tensor(label) else np.asarray(label)
     if image.ndim == 3:
         D, x, y = image.shape
         resize = (x != patch_size[0] or y != patch_size[1])
@@ -242,13 +352,63 @@ def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequ
     lab_d = torch.from_numpy(np.ascontiguousarray(label)).to(device)
     metric_list = [synapse_metric_percase(pred_d == c, lab_d == c) for c in range(1, classes)]
     if test_save_path is not None:
-        import os
-        os.makedirs(test_save_path, exist_ok=True)
-        for tag, vol in (("pred", prediction), ("img", image), ("gt", label)):
-            np.save(os.path.join(test_save_path, f"{case}_{tag}.npy"), np.asarray(vol, dtype=np.float32))
-        with open(os.path.join(test_save_path, f"{case}_spacing.txt"), "w") as f:
-            f.write(f"1 1 {z_spacing}\n")
+        _save_case(test_save_path, case, z_spacing, prediction, image, label)
     return metric_list
+
+
+@torch.no_grad()
+def val_single_volume(image, label, net, classes: int, patch_size: Sequence[int] = (224, 224), batch_slices: int = 32,
+                      device=None, resize: str = "device") -> List[float]:
+    """val_single_volume (metrics_eval.py:87-122): the prediction of `test_single_volume`, scored with calculate_dice_percase
+    only — Dice of classes 1..classes-1 over the whole volume.  `resize="device"`: the overlap counts come out of the argmax +
+    resize-back kernel, nothing but those 3 (K + 1) integers leaves the device.  `resize="host"` (and cases the device resize
+    does not take): the reference's host resizes, counts from the device."""
+    assert resize in ("host", "device"), resize
+    device = device or next(net.parameters()).device
+    net.eval()
+    on_dev = _device_case(image, label, device, patch_size) if resize == "device" else None
+    if on_dev is not None:
+        _, counts = predict_volume(net, on_dev[0], patch_size, batch_slices, labels=on_dev[1])
+        return class_dice(counts)[:classes - 1]
+    image = image.squeeze(0).cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
+    label = label.squeeze(0).cpu().numpy() if torch.is_tensor(label) else np.asarray(label)
+    assert image.ndim == 3, "volume [D,H,W] expected"
+    prediction = _predict_volume_host(net, image, label, patch_size, batch_slices, device)
+    pred_d = torch.from_numpy(np.ascontiguousarray(prediction)).to(device)
+    lab_d = torch.from_numpy(np.ascontiguousarray(label)).to(device)
+    out = []
+    for c in range(1, classes):  # calculate_dice_percase (metrics_eval.py:24-34)
+        p, g = pred_d == c, lab_d == c
+        np_, ng = int(p.sum()), int(g.sum())
+        out.append(2.0 * int((p & g).sum()) / (np_ + ng) if np_ > 0 and ng > 0 else (1.0 if np_ > 0 else 0.0))
+    return out
+
+
+@torch.no_grad()
+def inference(net, volumes, classes: int, patch_size: Sequence[int] = (224, 224), z_spacing: float = 1.0, test_save_path=None,
+              log=print, resize: str = "device", batch_slices: int = 32, device=None) -> Tuple[float, float]:
+    """inference (utils_acdc.py:7-33): `test_single_volume` for every case of `volumes` (the test loader's dicts: `image`
+    [1, D, H, W], `label`, `case_name` — a string or the DataLoader's one-element list), the reference's per-case and per-class
+    log lines through `log`, and (mean dice, mean hd95): the metric table averaged over the cases, then over the classes."""
+    net.eval()
+    total, n = 0.0, 0
+    for i, batch in enumerate(volumes):
+        case = batch["case_name"]
+        case = case[0] if isinstance(case, (list, tuple)) else case
+        m = test_single_volume(batch["image"], batch["label"], net, classes, patch_size=patch_size, batch_slices=batch_slices,
+                               device=device, resize=resize, test_save_path=test_save_path, case=case, z_spacing=z_spacing)
+        total = total + np.array(m, dtype=np.float64)
+        n += 1
+        mm = np.mean(m, axis=0)
+        log("idx %d case %s mean_dice %f mean_hd95 %f, mean_jacard %f mean_asd %f" % (i, case, mm[0], mm[1], mm[2], mm[3]))
+    if n == 0:
+        raise ValueError("inference: no test volumes")
+    table = total / n
+    for c in range(1, classes):
+        log("Mean class (%d) mean_dice %f mean_hd95 %f, mean_jacard %f mean_asd %f" % ((c,) + tuple(table[c - 1])))
+    performance, mean_hd95 = float(np.mean(table, axis=0)[0]), float(np.mean(table, axis=0)[1])
+    log("Testing performance in best val model) mean_dice:%f mean_hd95:%f" % (performance, mean_hd95))
+    return performance, mean_hd95
 
 
 def _binary_dc(result: torch.Tensor, reference: torch.Tensor) -> float:

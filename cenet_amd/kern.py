@@ -9,6 +9,7 @@ is bf16 while parameters, statistics and parameter gradients stay fp32.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -1225,6 +1226,40 @@ def augment_acdc(pool_img, pool_lab, tab, dp, stage_img, stage_lab, stage_stride
                                        C.c_int(max_h), C.c_int(max_w), P(out_img), P(out_lab), C.c_int(B), C.c_int(OH), C.c_int(OW),
                                        stream())
     _lib.check(rc, "cenet_augment_acdc")
+
+
+_SPLINE_POLE = math.sqrt(3.0) - 2.0  # the cubic B-spline prefilter's pole (scipy ni_splines)
+
+
+def vol_resize_supported(H: int, W: int, PH: int, PW: int) -> bool:
+    """scipy special-cases length-1 axes; the kernels do not"""
+    return min(H, W, PH, PW) >= 2
+
+
+def vol_resize_cubic(src, stage, out, n, H, W, PH, PW, normalize=None):
+    """cenet_vol_resize_cubic (volresize.hip): zoom(order=3) of n slices src [n, H, W] fp32 -> out [n, 1, PH, PW] fp32; stage: at
+    least n * H * W float64 of scratch; normalize = (mean, std) or None"""
+    _chk(src, out)
+    assert src.dtype == torch.float32 and out.dtype == torch.float32 and stage.dtype == torch.float64
+    assert src.is_contiguous() and out.is_contiguous() and stage.is_contiguous()
+    assert src.numel() >= n * H * W and stage.numel() >= n * H * W and out.numel() == n * PH * PW
+    mean, std = (float(normalize[0]), float(normalize[1])) if normalize is not None else (0.0, 1.0)
+    rc = _lib.lib().cenet_vol_resize_cubic(P(src), P(stage), P(out), C.c_int(n), C.c_int(H), C.c_int(W), C.c_int(PH), C.c_int(PW),
+                                           C.c_double(_SPLINE_POLE ** (H - 1)), C.c_double(_SPLINE_POLE ** (W - 1)),
+                                           C.c_int(int(normalize is not None)), C.c_float(mean), C.c_float(std), stream())
+    _lib.check(rc, "cenet_vol_resize_cubic")
+
+
+def argmax_resize_counts(logits, labels, pred, counts, n, K, PH, PW, H, W):
+    """cenet_argmax_resize_counts (volresize.hip): logits [n, K, PH, PW] fp32 / bf16 -> pred [n, H, W] class ids as float (argmax +
+    zoom(order=0) in one pass); with labels [n, H, W] float, counts [K + 1, 3] int32 as argmax_counts fills them"""
+    _chk(logits, labels, pred, counts)
+    assert logits.is_contiguous() and pred.is_contiguous() and pred.dtype == torch.float32
+    assert logits.numel() == n * K * PH * PW and pred.numel() == n * H * W
+    if labels is not None:
+        assert labels.dtype == torch.float32 and labels.is_contiguous() and labels.numel() == n * H * W
+        assert counts is not None and counts.dtype == torch.int32 and counts.numel() == (K + 1) * 3
+    _call("cenet_argmax_resize_counts_f32", logits, labels, pred, counts, n, K, PH, PW, H, W)
 
 
 def layernorm_fwd_acc(acc, bias, xpre, gamma, beta, y, mean, rstd, rows, Cn, eps):

@@ -14,9 +14,9 @@ What differs from the reference loop and why:
     replay (no host value is baked into the capture);
   * the epoch log line prints the reference's quantity — the sum of the batch losses over the number of training images
     (main_acdc.py:264-267) — but accumulated on the device and read back once per epoch;
-  * NOT here: the reference's `best.pth` / last-epoch checkpoint saves and its test inference after training
-    (main_acdc.py:272-289) — cenet_amd.checkpoint.save_weights / save_training_state and cenet_amd.evaluate are the pieces a caller
-    combines for that (tests/test_checkpoint.py, tests/test_evaluate.py); the loop returns the arena and the optimizer for it.
+  * the epoch tail of main_acdc.py:270-289 (test inference when the validation Dice does not fall, `best.pth`, the last-epoch
+    file) runs when `test_volumes` is given: cenet_amd.evaluate.inference with both resizes on the device, weights through
+    cenet_amd.checkpoint.save_weights.  The loop still returns the arena and the optimizer (save_training_state takes them).
 `train_acdc(..., graph=False)` is the same loop with eager launches: tests/test_train_loop.py holds the two against each other
 on changing batches."""
 from __future__ import annotations
@@ -38,13 +38,27 @@ def _as_batches(loader) -> Iterable[dict]:
 def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, base_lr: float = 0.05, momentum: float = 0.9,
                weight_decay: float = 1e-4, loss_type: str = "dice,ce", loss_weights: str = "0.5,0.5", device="cuda:0",
                graph: bool = True, val_batches: Optional[Callable[[], Iterable]] = None, log_every: int = 20,
-               log: Callable[[str], None] = print, optimizer: str = "sgd", scheduler: str = "poly") -> dict:
+               log: Callable[[str], None] = print, optimizer: str = "sgd", scheduler: str = "poly",
+               test_volumes: Optional[Callable[[], Iterable]] = None, save_dir: Optional[str] = None, img_size: int = 224,
+               test_resize: str = "device") -> dict:
     """main_acdc.py:200-290.  tr_loader yields {'image' [B,1,H,W] float, 'label' [B,H,W]} batches (host or device tensors);
     val_batches() yields (image [1,1,H,W], label [1,H,W]) pairs for the per-epoch validation (main_acdc.py:218-231).
     optimizer / scheduler: the reference's --optimizer / --scheduler strings (main_acdc.py:34-35, core.py:12-41); `momentum`
     applies to SGD, Adam / AdamW take betas (0.9, 0.999) and eps 1e-8 as the reference does.
-    -> {'loss': per-iteration losses read back at log points, 'epoch_loss': [...], 'val_dice': [...], 'lr': [...]}"""
-    from . import evaluate
+    test_volumes() yields the test loader's dicts (`image` [1,D,H,W], `label`, `case_name`) and needs val_batches: after an
+    epoch whose validation Dice is >= the best so far, evaluate.inference runs over them (slices resized to img_size, `test_resize`
+    as evaluate.test_single_volume takes it); only when its Dice is >= the best test Dice do BOTH bests move and `best.pth` is
+    written (main_acdc.py:272-278: a validation gain without a test gain moves neither); the last epoch writes
+    `epoch=<e>_lr=<lr>_avg_dcs=<last test dice>.pth` (:286-289).  Files go to save_dir (None: none are written).
+    -> {'loss': per-iteration losses read back at log points, 'epoch_loss': [...], 'val_dice': [...], 'lr': [...]} and, with
+    test_volumes, 'test_dice' / 'test_hd95' (one entry per inference run) and 'best_epochs' (epochs that wrote best.pth)"""
+    import os
+
+    from . import checkpoint, evaluate
+    if test_volumes is not None and val_batches is None:
+        raise ValueError("test_volumes: the test inference is gated by the validation Dice, pass val_batches too")
+    if save_dir is not None and test_volumes is None:
+        raise ValueError("save_dir: the checkpoints of main_acdc.py:272-289 are written by the test inference, pass test_volumes")
     dev = torch.device(device)
     net = net.to(dev).train()
     crit = losses.Criterion(num_classes, argparse.Namespace(loss_type=loss_type, loss_weights=loss_weights))
@@ -56,6 +70,10 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
     sched = optim.get_scheduler(opt, argparse.Namespace(scheduler=scheduler, base_lr=base_lr, max_epochs=max_epochs),
                                 max_iterations=max_epochs * len(tr_loader))
     hist = {"loss": [], "epoch_loss": [], "val_dice": [], "lr": []}
+    if test_volumes is not None:
+        hist.update(test_dice=[], test_hd95=[], best_epochs=[])
+    best_val = best_test = 0
+    te_dice = None
     static = {}
     stepper: List[Optional[G.GraphedStep]] = [None]
 
@@ -110,5 +128,27 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
         lr_last = hist["lr"][-1] if hist["lr"] else base_lr  # (an empty loader takes no step)
         log(f"epoch:{epoch:03d}/{max_epochs}, loss:{hist['epoch_loss'][-1]:0.5f}, lr:{lr_last:0.6f}"
             + (f", vl_DCS:{hist['val_dice'][-1] * 100:0.3f}" if hist["val_dice"] else ""))
+        if test_volumes is None:
+            continue
+        vl = hist["val_dice"][-1]
+        if vl >= best_val:
+            te_dice, te_hd = evaluate.inference(net, test_volumes(), num_classes, patch_size=(img_size, img_size), log=log,
+                                                resize=test_resize)
+            net.train()
+            if te_dice >= best_test:
+                best_val, best_test = vl, te_dice
+                hist["best_epochs"].append(epoch)
+                if save_dir is not None:
+                    os.makedirs(save_dir, exist_ok=True)
+                    checkpoint.save_weights(net, os.path.join(save_dir, "best.pth"))
+                    log(f"save model to {os.path.join(save_dir, 'best.pth')}")
+            hist["test_dice"].append(te_dice)
+            hist["test_hd95"].append(te_hd)
+            log(f"epoch:{epoch:03d}/{max_epochs}, te_DCS:{te_dice * 100:0.3f}, te_HD95:{te_hd:0.2f}")
+        if epoch >= max_epochs - 1 and save_dir is not None:
+            os.makedirs(save_dir, exist_ok=True)
+            path = os.path.join(save_dir, f"epoch={epoch}_lr={lr_last}_avg_dcs={te_dice}.pth")
+            checkpoint.save_weights(net, path)
+            log(f"save model to {path}")
     hist["arena"], hist["optimizer"] = arena, opt
     return hist

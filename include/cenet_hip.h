@@ -909,6 +909,24 @@ int cenet_augment_acdc(const float* pool_img, const unsigned char* pool_lab, con
                        unsigned char* stage_lab, long stage_stride, int max_h, int max_w, float* out_img, float* out_lab, int B,
                        int OH, int OW, cenet_stream_t stream);
 
+/* Test-time volume inference on the device (volresize.hip; src/utils/metrics_eval.py:37-84, utils_synapse.py:49-97).
+ * cenet_vol_resize_cubic: scipy.ndimage.zoom(slice, (PH / H, PW / W), order=3) for n slices src [n, H, W] fp32 -> out
+ * [n, 1, PH, PW] fp32, computed in fp64 in scipy's operation order (prefilter with mirror boundary along axis 0 then axis 1,
+ * coordinate o * ((H - 1) / (PH - 1)), cval = 0 above H - 1).  stage: n * H * W doubles of scratch.  zn_h = pole^(H-1), zn_w =
+ * pole^(W-1) with pole = sqrt(3) - 2, from the host as for cenet_augment_acdc.  normalize != 0: out = (float(v) - mean) / std in
+ * fp32.  H, W, PH, PW >= 2 (scipy special-cases length-1 axes), n <= 65535; CENET_EINVAL otherwise. */
+int cenet_vol_resize_cubic(const float* src, double* stage, float* out, int n, int H, int W, int PH, int PW, double zn_h,
+                           double zn_w, int normalize, float mean, float std, cenet_stream_t stream);
+/* pred [n, H, W] (class ids as floats) = zoom(argmax over K of logits [n, K, PH, PW], (H / PH, W / PW), order=0) without writing
+ * the [PH, PW] class map: output pixel (y, x) takes the first maximum over K at the source pixel floor(c + 0.5), c = index *
+ * ((PH - 1) / (H - 1)) in fp64, and 0 where c > PH - 1.  (H, W) == (PH, PW) is the plain argmax.  labels [n, H, W] (class ids as
+ * floats) and counts [(K+1)*3] (uint32, zero-filled by the call) as for cenet_argmax_counts_f32, both may be NULL together.
+ * K <= 16; H, W, PH, PW >= 2; CENET_EINVAL otherwise. */
+int cenet_argmax_resize_counts_f32(const float* logits, const float* labels, float* pred, unsigned* counts, int n, int K, int PH,
+                                   int PW, int H, int W, cenet_stream_t stream);
+int cenet_argmax_resize_counts_bf16(const unsigned short* logits, const float* labels, float* pred, unsigned* counts, int n, int K,
+                                    int PH, int PW, int H, int W, cenet_stream_t stream);
+
 /* LayerNorm of a split-K accumulator (norm.hip, round 5; pvtv2.py:93-95,99-100: sr conv -> norm): acc [rows, C] fp32 holds the
  * conv's products (zero-at-rest accumulator of a split-K GEMM); xpre = bf16(acc + bias) (the rows the LayerNorm backward reads),
  * y = LayerNorm(xpre) * gamma + beta, mean / rstd [rows]; acc is left zero.  bias may be NULL.  C % 4 == 0, C <= 512. */
