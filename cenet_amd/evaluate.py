@@ -12,7 +12,9 @@ produces the masks and the overlap counts (loss_optim.hip).
   * `calculate_metric_percase` of src/utils/metrics_eval.py:9-21 — (dice, hd95, jaccard, assd) per class  ->
     `metric_percase`, `test_single_volume`.  medpy's surface distances (border extraction + distance of every border voxel
     to the other border) run on the device in exact integer arithmetic (metrics.hip); only the final percentile / mean of
-    the few thousand distances is taken on the host, in float64 like numpy does.
+    the few thousand distances is taken on the host, in float64 like numpy does.  `label_metrics` scores all classes of a
+    volume from the two label maps at once; `method=` picks between the all-pairs minimum and the exact distance transform
+    (edt.hip), which is linear in the voxels and so also handles the noise an untrained network predicts.
 The scipy cubic `zoom` of slices that do not have the network's input size is the reference's own host-side dependency
 (metrics_eval.py:45,55); `resize="host"` (the default) calls it the same way, `resize="device"` runs both resizes on the device
 (csrc/volresize.hip through `predict_volume`: the volume is uploaded once and only the metric numbers come back).
@@ -119,39 +121,170 @@ def _directed_sq(a_pts: torch.Tensor, b_pts: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def surface_distances(result: torch.Tensor, reference: torch.Tensor) -> Tuple[np.ndarray, np.ndarray]:
+METHODS = ("auto", "edt", "pairs")
+_INT_MAX = 2 ** 31 - 1
+# method="auto": the transform when a class has more border-voxel pairs than this many per voxel of the union bounding box of its
+# two borders, the all-pairs kernel below that (DESIGN.md §9 has the scan behind the number: the two methods cross between 549 and
+# 741 pairs per box voxel on the MI355X, at about 640 by linear interpolation of the time differences)
+AUTO_PAIRS_PER_BOX_VOXEL = 640
+
+
+def _download(t: torch.Tensor) -> np.ndarray:
+    """the one device-to-host copy the label-map metrics go through (two calls per volume: the class table, the distances)"""
+    return t.cpu().numpy()
+
+
+def _label_table(pred: torch.Tensor, gt: torch.Tensor, classes: int):
+    """two label volumes [D,H,W] (or images [H,W]: medpy's 2-D rule, no z neighbours) -> (border labels of pred, of gt: uint8
+    [D,H,W], the voxel's class on that class's border, else 0; the per-class table of kern.label_borders as int64 numpy)"""
+    if pred.shape != gt.shape or pred.dim() not in (2, 3):
+        raise ValueError(f"two label volumes [D,H,W] or images [H,W] of one shape expected, got {tuple(pred.shape)}, {tuple(gt.shape)}")
+    if not 2 <= classes <= 64:
+        raise ValueError(f"2 <= classes <= 64 expected, got {classes}")
+    zfaces = pred.dim() == 3
+    if not zfaces:
+        pred, gt = pred.unsqueeze(0), gt.unsqueeze(0)
+    pred, gt = pred.float().contiguous(), gt.float().contiguous()
+    D, H, W = pred.shape
+    blp = torch.empty((D, H, W), dtype=torch.uint8, device=pred.device)
+    blg = torch.empty_like(blp)
+    table = torch.zeros((classes, kern.LB_COLS), dtype=torch.int32, device=pred.device)
+    table[:, 5:] = _INT_MAX
+    kern.label_borders(pred, gt, blp, blg, table, classes, D, H, W, zfaces)
+    return blp, blg, _download(table).astype(np.int64)
+
+
+def _border_offsets(bl: torch.Tensor, c: int, n: int) -> torch.Tensor:
+    counts = torch.empty((n + kern.CP_CHUNK - 1) // kern.CP_CHUNK, dtype=torch.int32, device=bl.device)
+    kern.border_count(bl, c, n, counts)
+    return (torch.cumsum(counts, 0) - counts).to(torch.int32)
+
+
+def _surface_sq(blp: torch.Tensor, blg: torch.Tensor, tab: np.ndarray, todo: Sequence[int], method: str):
+    """squared surface distances of the classes `todo` (both masks non-empty): {c: (pred border -> gt border, gt border -> pred
+    border)} as int32 numpy arrays in C order of the border voxels.  Everything is queued without a synchronisation, sized from
+    the table; one download at the end brings all the arrays."""
+    if not todo:
+        return {}
+    dev = blp.device
+    plan, total, scratch = [], 0, 0
+    for c in todo:
+        row = [int(v) for v in tab[c]]
+        na, nb = row[3], row[4]
+        lo = [min(row[5 + k], row[11 + k]) for k in range(3)]
+        hi = [max(-row[8 + k], -row[14 + k]) for k in range(3)]
+        box = [h - l + 1 for l, h in zip(lo, hi)]
+        vol = box[0] * box[1] * box[2]
+        edt = method == "edt" or (method == "auto" and na * nb > AUTO_PAIRS_PER_BOX_VOXEL * vol and kern.edt_supported(*box))
+        plan.append((c, na, nb, lo, box, vol, edt, total))
+        total += na + nb
+        scratch = max(scratch, vol if edt else 0)
+    out = torch.full((total,), _INT_MAX, dtype=torch.int32, device=dev)
+    tmp = torch.empty(scratch, dtype=torch.int32, device=dev) if scratch else None
+    d2 = torch.empty(scratch, dtype=torch.int32, device=dev) if scratch else None
+    for c, na, nb, lo, box, vol, edt, off in plan:
+        # the union bounding box of the two borders holds every query and every feature voxel, so the transform of the crop equals
+        # the transform of the volume at every query voxel
+        a = blp[lo[0]:lo[0] + box[0], lo[1]:lo[1] + box[1], lo[2]:lo[2] + box[2]].contiguous()
+        b = blg[lo[0]:lo[0] + box[0], lo[1]:lo[1] + box[1], lo[2]:lo[2] + box[2]].contiguous()
+        offs_a, offs_b = _border_offsets(a, c, vol), _border_offsets(b, c, vol)
+        oa, ob = out[off:off + na], out[off + na:off + na + nb]
+        if edt:
+            kern.edt_sq_raw(b, c, tmp, d2, *box)
+            kern.border_gather(a, c, *box, offs_a, d2, oa)
+            kern.edt_sq_raw(a, c, tmp, d2, *box)
+            kern.border_gather(b, c, *box, offs_b, d2, ob)
+        else:
+            pa = torch.empty((na, 3), dtype=torch.int32, device=dev)
+            pb = torch.empty((nb, 3), dtype=torch.int32, device=dev)
+            kern.border_gather(a, c, *box, offs_a, None, pa)
+            kern.border_gather(b, c, *box, offs_b, None, pb)
+            kern.min_sqdist(pa, pb, oa)
+            kern.min_sqdist(pb, pa, ob)
+    arr = _download(out)
+    return {c: (arr[off:off + na], arr[off + na:off + na + nb]) for c, na, nb, _, _, _, _, off in plan}
+
+
+def _sqrt64(sq: np.ndarray) -> np.ndarray:
+    return np.sqrt(sq.astype(np.float64))
+
+
+def label_metrics(pred: torch.Tensor, gt: torch.Tensor, classes: int, kind: str = "acdc", method: str = "auto"):
+    """The per-class metric loop of test_single_volume (metrics_eval.py:60-62, utils_synapse.py:80-82) from the two label
+    volumes [D,H,W] (or images [H,W]) directly: [(dice, hd95, jaccard, assd)] (kind="acdc", calculate_metric_percase of
+    metrics_eval.py:9-21) or [(dice, hd95)] (kind="synapse", utils_synapse.py:12-21) for classes 1..classes-1, with the
+    reference's rules for empty masks.  One kernel pass yields every class's borders, counts and bounding boxes; two downloads per
+    volume (that table, then all the distance arrays) whatever `classes` is.  `method`: see `surface_distances`, chosen per class."""
+    assert kind in ("acdc", "synapse"), kind
+    assert method in METHODS, method
+    blp, blg, tab = _label_table(pred, gt, classes)
+    todo = [c for c in range(1, classes) if tab[c, 1] > 0 and tab[c, 2] > 0]
+    sq = _surface_sq(blp, blg, tab, todo, method)
+    res = []
+    for c in range(1, classes):
+        inter, np_, ng = (int(v) for v in tab[c, :3])
+        if c in sq:
+            d1, d2 = _sqrt64(sq[c][0]), _sqrt64(sq[c][1])
+            dice = 2.0 * inter / float(np_ + ng)
+            h95 = float(np.percentile(np.hstack((d1, d2)), 95))
+            if kind == "acdc":
+                res.append((dice, h95, inter / float(np_ + ng - inter), float(np.mean((d1.mean(), d2.mean())))))
+            else:
+                res.append((dice, h95))
+        elif np_ > 0 and ng == 0:
+            res.append((1, 0, 1, 0) if kind == "acdc" else (1, 0))
+        else:
+            res.append((0, 0, 0, 0) if kind == "acdc" else (0, 0))
+    return res
+
+
+def surface_distances(result: torch.Tensor, reference: torch.Tensor, method: str = "auto") -> Tuple[np.ndarray, np.ndarray]:
     """Both directed surface-distance sets (result->reference, reference->result) as float64 arrays, unit voxel spacing.
-    Raises RuntimeError on an empty mask, as medpy does."""
-    ra, rb = surface_points(result), surface_points(reference)
-    if ra.shape[0] == 0:
+    Raises RuntimeError on an empty mask, as medpy does.  method="pairs": every border voxel against every border voxel of the
+    other mask (metrics.hip); "edt": the exact distance transform of one border read at the other (edt.hip), over the union
+    bounding box of the two; "auto": whichever the sizes favour.  The arrays are identical either way."""
+    assert method in METHODS, method
+    if method == "pairs" or (method == "auto" and (result.shape != reference.shape or result.dim() not in (2, 3))):
+        ra, rb = surface_points(result), surface_points(reference)
+        if ra.shape[0] == 0:
+            raise RuntimeError("The first supplied array does not contain any binary object.")
+        if rb.shape[0] == 0:
+            raise RuntimeError("The second supplied array does not contain any binary object.")
+        d1 = _directed_sq(ra, rb).cpu().numpy().astype(np.float64)
+        d2 = _directed_sq(rb, ra).cpu().numpy().astype(np.float64)
+        return np.sqrt(d1), np.sqrt(d2)
+    blp, blg, tab = _label_table(result != 0, reference != 0, 2)
+    if tab[1, 1] == 0:
         raise RuntimeError("The first supplied array does not contain any binary object.")
-    if rb.shape[0] == 0:
+    if tab[1, 2] == 0:
         raise RuntimeError("The second supplied array does not contain any binary object.")
-    d1 = _directed_sq(ra, rb).cpu().numpy().astype(np.float64)
-    d2 = _directed_sq(rb, ra).cpu().numpy().astype(np.float64)
-    return np.sqrt(d1), np.sqrt(d2)
+    sq = _surface_sq(blp, blg, tab, [1], method)[1]
+    return _sqrt64(sq[0]), _sqrt64(sq[1])
 
 
-def hd95(result: torch.Tensor, reference: torch.Tensor) -> float:
-    d1, d2 = surface_distances(result, reference)
+def hd95(result: torch.Tensor, reference: torch.Tensor, method: str = "auto") -> float:
+    d1, d2 = surface_distances(result, reference, method)
     return float(np.percentile(np.hstack((d1, d2)), 95))
 
 
-def assd(result: torch.Tensor, reference: torch.Tensor) -> float:
-    d1, d2 = surface_distances(result, reference)
+def assd(result: torch.Tensor, reference: torch.Tensor, method: str = "auto") -> float:
+    d1, d2 = surface_distances(result, reference, method)
     return float(np.mean((d1.mean(), d2.mean())))
 
 
-def metric_percase(pred: torch.Tensor, gt: torch.Tensor) -> Tuple[float, float, float, float]:
+def metric_percase(pred: torch.Tensor, gt: torch.Tensor, method: str = "auto") -> Tuple[float, float, float, float]:
     """calculate_metric_percase (metrics_eval.py:9-21): (dice, hd95, jaccard, assd) of two binary volumes, with its rules
     for empty masks."""
+    assert method in METHODS, method
+    if method != "pairs" and pred.shape == gt.shape and pred.dim() in (2, 3):
+        return label_metrics(pred != 0, gt != 0, 2, "acdc", method)[0]
     p, g = pred != 0, gt != 0
     np_, ng = int(p.sum()), int(g.sum())
     if np_ > 0 and ng > 0:
         inter = int((p & g).sum())
         dice = 2.0 * inter / float(np_ + ng)
         jac = inter / float(np_ + ng - inter)
-        d1, d2 = surface_distances(p, g)
+        d1, d2 = surface_distances(p, g, method)
         return dice, float(np.percentile(np.hstack((d1, d2)), 95)), jac, float(np.mean((d1.mean(), d2.mean())))
     if np_ > 0 and ng == 0:
         return 1, 0, 1, 0
@@ -264,7 +397,7 @@ def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int
         pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices)
         if test_save_path is not None:
             _save_case(test_save_path, case, z_spacing, pred_d, on_dev[0], on_dev[1])
-        return [metric_percase(pred_d == c, on_dev[1] == c) for c in range(1, classes)]
+        return label_metrics(pred_d, on_dev[1], classes, "acdc")
     image = image.squeeze(0).cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
     label = label.squeeze(0).cpu().numpy() if torch.is_tensor(label) else np.asarray(label)
     assert image.ndim == 3, "volume [D,H,W] expected"
@@ -286,20 +419,23 @@ def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int
     lab_d = torch.from_numpy(np.ascontiguousarray(label)).to(device)
     if test_save_path is not None:
         _save_case(test_save_path, case, z_spacing, prediction, image, label)
-    return [metric_percase(pred_d == c, lab_d == c) for c in range(1, classes)]
+    return label_metrics(pred_d, lab_d, classes, "acdc")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # Synapse (utils/utils_synapse.py:12-100) and skin (utils/utils_skin.py:97-170) evaluation wrappers
 # ---------------------------------------------------------------------------------------------------------------------------
-def synapse_metric_percase(pred: torch.Tensor, gt: torch.Tensor) -> Tuple[float, float]:
+def synapse_metric_percase(pred: torch.Tensor, gt: torch.Tensor, method: str = "auto") -> Tuple[float, float]:
     """calculate_metric_percase of utils_synapse.py:12-21: (dice, hd95) of two binary volumes; (1, 0) for a prediction without
     ground truth, (0, 0) otherwise."""
+    assert method in METHODS, method
+    if method != "pairs" and pred.shape == gt.shape and pred.dim() in (2, 3):
+        return label_metrics(pred != 0, gt != 0, 2, "synapse", method)[0]
     p, g = pred != 0, gt != 0
     np_, ng = int(p.sum()), int(g.sum())
     if np_ > 0 and ng > 0:
         inter = int((p & g).sum())
-        d1, d2 = surface_distances(p, g)
+        d1, d2 = surface_distances(p, g, method)
         return 2.0 * inter / float(np_ + ng), float(np.percentile(np.hstack((d1, d2)), 95))
     if np_ > 0 and ng == 0:
         return 1, 0
@@ -325,7 +461,7 @@ def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequ
         pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices, normalize=(0.5, 0.5))
         if test_save_path is not None:
             _save_case(test_save_path, case, z_spacing, pred_d, on_dev[0], on_dev[1])
-        return [synapse_metric_percase(pred_d == c, on_dev[1] == c) for c in range(1, classes)]
+        return label_metrics(pred_d, on_dev[1], classes, "synapse")
     image = image.squeeze(0).cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
     label = label.squeeze(0).cpu().numpy() if torch.is_tensor(label) else np.asarray(label)
     if image.ndim == 3:
@@ -350,7 +486,7 @@ def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequ
         prediction = pred.squeeze(0).cpu().numpy().astype(label.dtype)
     pred_d = torch.from_numpy(np.ascontiguousarray(prediction)).to(device)
     lab_d = torch.from_numpy(np.ascontiguousarray(label)).to(device)
-    metric_list = [synapse_metric_percase(pred_d == c, lab_d == c) for c in range(1, classes)]
+    metric_list = label_metrics(pred_d, lab_d, classes, "synapse")
     if test_save_path is not None:
         _save_case(test_save_path, case, z_spacing, prediction, image, label)
     return metric_list

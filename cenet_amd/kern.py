@@ -1023,6 +1023,50 @@ def min_sqdist(a_i32, b_i32, out_i32):
     _call("cenet_min_sqdist_i32", a_i32, a_i32.shape[0], b_i32, b_i32.shape[0], out_i32)
 
 
+LB_COLS = 17  # CENET_LB_COLS
+CP_CHUNK = 4096  # voxels per workgroup of the border compaction (csrc/edt.hip)
+
+
+def edt_supported(D, H, W) -> bool:
+    return D > 0 and H > 0 and W > 0 and D * D + H * H + W * W < 2 ** 31
+
+
+def edt_sq_raw(feat_u8, match, tmp_i32, d2_i32, D, H, W):
+    """cenet_edt_sq_u8 without the feature check: d2 = INT_MAX everywhere when no voxel of feat_u8 is a feature"""
+    _chk(feat_u8, tmp_i32, d2_i32)
+    if not edt_supported(D, H, W):
+        raise ValueError(f"the distance transform needs D^2 + H^2 + W^2 < 2^31, got {(D, H, W)}")
+    _call("cenet_edt_sq_u8", feat_u8, int(match), tmp_i32, d2_i32, D, H, W)
+
+
+def edt_sq(feat_u8: torch.Tensor) -> torch.Tensor:
+    """exact squared Euclidean distance transform: feat_u8 [D,H,W] uint8 (non-zero = feature voxel) -> int32 [D,H,W],
+    d2[v] = min over feature voxels f of |v - f|^2 (unit spacing).  A volume without a feature voxel is refused."""
+    assert feat_u8.dim() == 3 and feat_u8.dtype == torch.uint8, "uint8 [D,H,W] expected"
+    feat_u8 = feat_u8.contiguous()
+    if not bool(feat_u8.any()):
+        raise ValueError("edt_sq: the volume has no feature voxel")
+    d2 = torch.empty(feat_u8.shape, dtype=torch.int32, device=feat_u8.device)
+    edt_sq_raw(feat_u8, -1, torch.empty_like(d2), d2, *feat_u8.shape)
+    return d2
+
+
+def label_borders(pred_f32, gt_f32, border_pred_u8, border_gt_u8, table_i32, K, D, H, W, zfaces=True):
+    _chk(pred_f32, gt_f32, border_pred_u8, border_gt_u8, table_i32)
+    _call("cenet_label_borders_f32", pred_f32, gt_f32, border_pred_u8, border_gt_u8, table_i32, K, D, H, W, bool(zfaces))
+
+
+def border_count(bl_u8, match, n, counts_i32):
+    _chk(bl_u8, counts_i32)
+    _call("cenet_border_count_u8", bl_u8, int(match), L(n), counts_i32)
+
+
+def border_gather(bl_u8, match, D, H, W, offs_i32, src_i32, out_i32):
+    """src_i32 None: out gets the (z, y, x) rows of the matching voxels; else src at those voxels — both in C order"""
+    _chk(bl_u8, offs_i32, src_i32, out_i32)
+    _call("cenet_border_gather_i32", bl_u8, int(match), D, H, W, offs_i32, src_i32, out_i32)
+
+
 def sgd_step(p, g, buf, hyper5, n, shadow=None):
     """shadow: bf16 copy of the parameters, rewritten by the same kernel (the GEMM operand of the throughput mode)"""
     _chk(p, g, buf, hyper5, shadow)

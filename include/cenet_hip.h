@@ -542,6 +542,25 @@ int cenet_surface_border_u8(const unsigned char* mask, unsigned char* border, in
  * reference's calls use; out [na] int32 pre-filled by the caller with INT_MAX. The distance transform of medpy's
  * __surface_distances sampled at the other surface, kept in exact integer arithmetic (host takes the square root). */
 int cenet_min_sqdist_i32(const int* a, int na, const int* b, int nb, int* out, cenet_stream_t stream);
+/* The same distances by an exact distance transform (csrc/edt.hip): linear in the number of voxels instead of quadratic in the
+ * border sizes.  d2[v] = min over feature voxels f of |v - f|^2 for a uint8 volume [D,H,W], unit spacing, int32, exact.  A voxel
+ * is a feature when it is non-zero (match < 0) or equals `match` (0..255).  tmp and d2: D*H*W int32 each; the result is in d2,
+ * INT_MAX everywhere when there is no feature voxel.  CENET_EINVAL unless D^2 + H^2 + W^2 < 2^31. */
+int cenet_edt_sq_u8(const unsigned char* feat, int match, int* tmp, int* d2, int D, int H, int W, cenet_stream_t stream);
+/* One pass over two label volumes (class ids as float, anything that is not an integer in [1, K) is background): border_pred /
+ * border_gt [D*H*W] = the voxel's class where it is a border voxel of that class (a face neighbour differs or lies outside;
+ * zfaces = 0 leaves the z neighbours out: medpy's rule for a 2-D mask, passed as D = 1), else 0.  table [K, CENET_LB_COLS] int32,
+ * row c: |pred==c & gt==c|, |pred==c|, |gt==c|, |border pred|, |border gt|, then per border min z, y, x and min -z, -y, -x.
+ * The caller zeroes columns 0-4 and fills the rest with INT_MAX.  2 <= K <= 64. */
+#define CENET_LB_COLS 17
+int cenet_label_borders_f32(const float* pred, const float* gt, unsigned char* border_pred, unsigned char* border_gt, int* table,
+                            int K, int D, int H, int W, int zfaces, cenet_stream_t stream);
+/* Order-preserving compaction of the voxels of bl [n] that equal `match`, in two launches: counts[b] = matches among the voxels
+ * [4096 b, 4096 b + 4096); then, with offs = the exclusive prefix sum of counts, out[rank] = src[voxel] (src != NULL) or
+ * out[3 rank ..] = (z, y, x) of the voxel (src == NULL), rank in C order. */
+int cenet_border_count_u8(const unsigned char* bl, int match, long n, int* counts, cenet_stream_t stream);
+int cenet_border_gather_i32(const unsigned char* bl, int match, int D, int H, int W, const int* offs, const int* src, int* out,
+                            cenet_stream_t stream);
 /* torch.optim.SGD(momentum, weight_decay) over a flat arena; hyper5 (device) = [lr, momentum, wd, grad_scale, first_step] */
 int cenet_sgd_step_f32(float* p, const float* g, float* buf, const float* hyper5, long n, cenet_stream_t stream);
 /* torch.optim.Adam / AdamW (amsgrad off) over a flat arena, one pass; exp_avg / exp_avg_sq are the flat fp32 moment buffers.

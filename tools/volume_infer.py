@@ -6,9 +6,14 @@ ACDC preset with the oracle's deterministic weights (seed 42), one ACDC-like vol
 median and spread reported), then three instrumented calls in which every part is wrapped with a synchronize on both sides (the
 split; its parts do not overlap, so their sum is above the plain call's time; `other` is what the wrappers do not cover: uploads,
 the host path's argmax and device-to-host copy, Python).  The surface-distance metrics compare every border voxel of one mask with
-every border voxel of the other; with random weights a prediction can be noise with millions of border voxels, so above
---metrics-cap pairs the metrics are stubbed out (in BOTH modes) and the line says so.  Prints one JSON line.
-    python tools/volume_infer.py [--bf16] [--only acdc|synapse] [--metrics-cap 5e10]"""
+every border voxel of the other (--metrics pairs); with random weights a prediction can be noise with millions of border voxels, so
+above --metrics-cap pairs the metrics are stubbed out (in BOTH modes) and the line says so.  The cap applies to `pairs` only:
+--metrics edt (the exact distance transform, csrc/edt.hip) and auto are linear in the voxels and always timed.
+--report adds the metrics alone (`evaluate.label_metrics` on label volumes that are already on the device; one warm-up, median of
+five, spread, all methods in this one process): per volume size the network's prediction and a uniform-noise prediction against the
+blob labels, under the parent's per-class `metric_percase(method="pairs")` loop, `pairs`, `edt` and `auto`; and the crossover scan
+behind `evaluate.AUTO_PAIRS_PER_BOX_VOXEL`: two overlapping balls of growing radius under both methods.  Prints one JSON line.
+    python tools/volume_infer.py [--bf16] [--only acdc|synapse] [--metrics pairs|edt|auto] [--metrics-cap 5e10] [--report]"""
 import argparse
 import json
 import os
@@ -70,20 +75,92 @@ def call(net, image, label, mode, dev):
 def split_call(net, image, label, mode, dev):
     """one call with every part wrapped; the wrappers are taken off again"""
     p = Parts()
-    saved = (scipy.ndimage.zoom, kern.vol_resize_cubic, kern.argmax_resize_counts, evaluate.metric_percase, net.forward)
+    saved = (scipy.ndimage.zoom, kern.vol_resize_cubic, kern.argmax_resize_counts, evaluate.label_metrics, net.forward)
     scipy.ndimage.zoom = p.wrap(lambda *a, **k: "resize_in" if k.get("order", 3) == 3 else "resize_back", saved[0])
     kern.vol_resize_cubic = p.wrap("resize_in", saved[1])
     kern.argmax_resize_counts = p.wrap("resize_back", saved[2])
-    evaluate.metric_percase = p.wrap("metrics", saved[3])
+    evaluate.label_metrics = p.wrap("metrics", saved[3])
     net.forward = p.wrap("forward", saved[4])
     try:
         total, _ = call(net, image, label, mode, dev)
     finally:
-        scipy.ndimage.zoom, kern.vol_resize_cubic, kern.argmax_resize_counts, evaluate.metric_percase = saved[:4]
+        scipy.ndimage.zoom, kern.vol_resize_cubic, kern.argmax_resize_counts, evaluate.label_metrics = saved[:4]
         del net.forward
     p.t["other"] = total - sum(p.t.values())
     p.t["total"] = total
     return p.t
+
+
+def timed(fn, reps=5):
+    """one warm-up, then `reps` calls with a synchronize on both sides: {median, spread, runs} in ms"""
+    fn()
+    runs = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        runs.append((time.perf_counter() - t0) * 1e3)
+    return {"median": round(statistics.median(runs), 3), "spread": round(max(runs) - min(runs), 3), "runs": [round(v, 3) for v in runs]}
+
+
+def border_pairs(pred, lab, classes):
+    """largest border-pair count of a class and the totals, from the table label_metrics itself works from"""
+    _, _, tab = evaluate._label_table(pred, lab, classes)
+    return max(int(tab[c, 3]) * int(tab[c, 4]) for c in range(1, classes)), int(tab[1:, 3].sum()), int(tab[1:, 4].sum())
+
+
+def metrics_report(net, dev, cap, only):
+    """the metrics alone, every method in this process"""
+    rep = {"volumes": {}, "crossover": []}
+    for name, shape in VOLUMES.items():
+        if only and name != only:
+            continue
+        image, label = make_volume(shape, seed=sum(shape))
+        lab = label[0].to(dev)
+        net_pred, _ = evaluate.predict_volume(net, image[0].to(dev), PATCH)
+        noise = torch.from_numpy(np.random.default_rng(1).integers(0, K, shape).astype(np.float32)).to(dev)
+        for tag, pred in (("net_pred", net_pred), ("noise_pred", noise)):
+            pairs, nbp, nbg = border_pairs(pred, lab, K)
+            e = {"shape": list(shape), "classes": K, "max_border_pairs": pairs, "border_voxels_pred": nbp, "border_voxels_gt": nbg}
+            if pairs <= cap:
+                e["parent_per_class_loop"] = timed(lambda: [evaluate.metric_percase(pred == c, lab == c, method="pairs")
+                                                            for c in range(1, K)])
+                e["pairs"] = timed(lambda: evaluate.label_metrics(pred, lab, K, method="pairs"))
+            else:
+                e["parent_per_class_loop"] = e["pairs"] = "capped"
+            e["edt"] = timed(lambda: evaluate.label_metrics(pred, lab, K, method="edt"))
+            e["auto"] = timed(lambda: evaluate.label_metrics(pred, lab, K, method="auto"))
+            if pairs <= cap:
+                e["equal"] = evaluate.label_metrics(pred, lab, K, method="pairs") == evaluate.label_metrics(pred, lab, K, method="edt")
+            rep["volumes"][f"{name}/{tag}"] = e
+        if name == "synapse":  # noise against noise with the Synapse class count: every class of both volumes is all border
+            rng = np.random.default_rng(2)
+            p9, g9 = (torch.from_numpy(rng.integers(0, 9, shape).astype(np.float32)).to(dev) for _ in range(2))
+            pairs, nbp, nbg = border_pairs(p9, g9, 9)
+            rep["volumes"]["synapse/noise_vs_noise_k9"] = {
+                "shape": list(shape), "classes": 9, "max_border_pairs": pairs, "border_voxels_pred": nbp, "border_voxels_gt": nbg,
+                "parent_per_class_loop": "capped", "pairs": "capped",
+                "edt": timed(lambda: evaluate.label_metrics(p9, g9, 9, kind="synapse", method="edt"))}
+            del p9, g9
+    if not only:
+        # crossover: two overlapping balls in 160 x 256 x 256, one class; cost estimate of `auto` = na * nb against the box volume
+        D, H, W = 160, 256, 256
+        zz, yy, xx = np.ogrid[:D, :H, :W]
+        for r in (3, 6, 12, 24, 36, 48, 64, 72):
+            a = ((zz - 80) ** 2 + (yy - 128) ** 2 + (xx - 120) ** 2 <= r * r).astype(np.float32)
+            b = ((zz - 80) ** 2 + (yy - 128) ** 2 + (xx - 120 - max(1, r // 4)) ** 2 <= r * r).astype(np.float32)
+            ta, tb = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
+            _, _, tab = evaluate._label_table(ta, tb, 2)
+            row = [int(v) for v in tab[1]]
+            box = [max(-row[8 + k], -row[14 + k]) - min(row[5 + k], row[11 + k]) + 1 for k in range(3)]
+            vol = box[0] * box[1] * box[2]
+            p = timed(lambda: evaluate.label_metrics(ta, tb, 2, method="pairs"))
+            e = timed(lambda: evaluate.label_metrics(ta, tb, 2, method="edt"))
+            rep["crossover"].append({"radius": r, "na": row[3], "nb": row[4], "box": box, "pairs_per_box_voxel": round(row[3] * row[4] / vol, 2),
+                                     "pairs_ms": p["median"], "pairs_spread": p["spread"], "edt_ms": e["median"], "edt_spread": e["spread"]})
+    rep["auto_pairs_per_box_voxel"] = evaluate.AUTO_PAIRS_PER_BOX_VOXEL
+    return rep
 
 
 def main():
@@ -91,6 +168,8 @@ def main():
     ap.add_argument("--bf16", action="store_true")
     ap.add_argument("--only", choices=sorted(VOLUMES))
     ap.add_argument("--metrics-cap", type=float, default=5e10)
+    ap.add_argument("--metrics", choices=evaluate.METHODS, default="auto")
+    ap.add_argument("--report", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     kw = MODEL_CONFIGS["acdc"]["kw"]
@@ -99,8 +178,8 @@ def main():
     net = net.to(dev).eval()
     kern.set_compute_bf16(args.bf16)
     res = {"tool": "volume_infer", "device": torch.cuda.get_device_name(0), "kernel_src_sha16": build.source_sha16(),
-           "precision": "bf16" if args.bf16 else "fp32", "patch": list(PATCH), "batch_slices": 32, "unit": "ms", "volumes": {}}
-    real_metric = evaluate.metric_percase
+           "precision": "bf16" if args.bf16 else "fp32", "patch": list(PATCH), "batch_slices": 32, "unit": "ms", "metrics_method": args.metrics, "volumes": {}}
+    real_metric = evaluate.label_metrics
     for name, shape in VOLUMES.items():
         if args.only and name != args.only:
             continue
@@ -108,13 +187,12 @@ def main():
         # how much work the surface metrics would be on this prediction
         pred, _ = evaluate.predict_volume(net, image[0].to(dev), PATCH)
         lab_d = label[0].to(dev)
-        pairs = 0
-        for c in range(1, K):
-            na, nb = (int(evaluate.surface_points(v == c).shape[0]) for v in (pred, lab_d))
-            pairs = max(pairs, na * nb)
-        timed_metrics = pairs <= args.metrics_cap
-        if not timed_metrics:
-            evaluate.metric_percase = lambda p, g: (0.0, 0.0, 0.0, 0.0)
+        pairs = border_pairs(pred, lab_d, K)[0]
+        timed_metrics = args.metrics != "pairs" or pairs <= args.metrics_cap
+        if timed_metrics:
+            evaluate.label_metrics = lambda p, g, k, kind="acdc", method=args.metrics: real_metric(p, g, k, kind, method)
+        else:
+            evaluate.label_metrics = lambda p, g, k, kind="acdc", method=None: [(0.0, 0.0, 0.0, 0.0)] * (k - 1)
         entry = {"shape": list(shape), "max_border_pairs": pairs, "metrics_timed": timed_metrics}
         preds = {}
         for mode in ("host", "device"):
@@ -126,11 +204,13 @@ def main():
                            "total_spread": round(max(runs) - min(runs), 3),
                            "split_median": {k: round(statistics.median(s.get(k, 0.0) for s in splits), 3) for k in keys}}
             preds[mode] = evaluate.val_single_volume(image, label, net, K, patch_size=PATCH, device=dev, resize=mode)
-        evaluate.metric_percase = real_metric
+        evaluate.label_metrics = real_metric
         entry["speedup"] = round(entry["host"]["total_median"] / entry["device"]["total_median"], 3)
         entry["class_dice"] = {m: [round(v, 6) for v in preds[m]] for m in preds}
         entry["class_dice_equal"] = preds["host"] == preds["device"]
         res["volumes"][name] = entry
+    if args.report:
+        res["metrics"] = metrics_report(net, dev, args.metrics_cap, args.only)
     print(json.dumps(res))
 
 
