@@ -109,7 +109,9 @@ def test_conv_igemm_fwd_dgrad_wgrad(dev, k, stride, pad, dil):
 
 @pytest.mark.parametrize("M,N,K", [(200, 150, 100), (32, 300, 70), (130, 64, 129), (65, 33, 160)])
 def test_gemm_tiles_fp32_and_bf16(dev, M, N, K):
-    """larger shapes exercise the 128x128 / 32x256 tiles; bf16-operand mode is checked against bf16-rounded inputs."""
+    """ragged shapes on the 64x64 / 32x256 / 32x64 tiles (one launch of these sizes never fills 256 workgroups, so pick_tile drops
+    the 128-wide tiles to 64x64: those are reached by tests/test_gemm_bounds.py); bf16-operand mode is checked against
+    bf16-rounded inputs."""
     x, w, b = rnd(M, K, dev=dev), rnd(N, K, dev=dev, seed=1), rnd(N, dev=dev, seed=2)
     y = torch.empty(M, N, device=dev)
     kern.gemm(kern.mat_plain(x, K, 1, kfast=1), kern.mat_plain(w, 1, K, kfast=1), y, M, N, K, scr=N, scc=1, bias=b)
@@ -214,8 +216,7 @@ def test_ring_stream_orientations(dev, akf, bkf, K):
     B = kern.mat_plain(bt, 1, K, kfast=1) if bkf else kern.mat_plain(b, N, 1, kfast=0)
     y = torch.empty(M, N, device=dev, dtype=BF)
     kern.gemm(A, B, y, M, N, K, scr=N, scc=1)
-    if not kern._lib.is_hostsim():
-        assert kern.last_gemm_kernel().startswith("gemm_ring_stream_kernel"), kern.last_gemm_kernel()
+    assert kern.last_gemm_kernel().startswith("gemm_ring_stream_kernel"), kern.last_gemm_kernel()
     ref = a.float() @ b.float()
     torch.testing.assert_close(y.float().cpu(), ref.cpu(), rtol=2e-2, atol=2e-2 * ref.abs().max().item())
     assert (y.float() - ref).abs().mean().item() < 4e-3 * ref.abs().mean().item()

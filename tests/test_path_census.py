@@ -10,6 +10,7 @@ where the fused path is expected.  The census was taken on the MI355X with `pyth
 """
 import argparse
 import collections
+import contextlib
 import os
 import sys
 
@@ -21,23 +22,16 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def census(preset: str):
+@contextlib.contextmanager
+def warm_step(preset: str):
+    """The benched configuration of a preset on the MI355X: bf16 throughput mode, the model, criterion and optimizer of bench.py at the
+    preset's baseline batch.  Yields `step` (zero_grad, forward, backward, optimizer step) after one warm-up step has run (lazy
+    buffers, merged parameters); also the set-up of the GEMM step replay (tests/test_gemm_replay.py)."""
     import bench
     from cenet_amd import kern, losses, optim
     dev = torch.device("cuda:0")
     cfg = bench.CONFIGS[preset]
     old = kern.set_compute_bf16(True)
-    counts = collections.Counter()
-    saved = {}
-
-    def count(name, fn, label):
-        saved[name] = fn
-
-        def f(*a, **k):
-            counts[label(*a, **k)] += 1
-            return fn(*a, **k)
-        setattr(kern, name, f)
-
     try:
         net = bench.make_model(dev, cfg)
         x, lab = bench.synthetic(cfg["batch"], dev, 0, cfg)
@@ -52,19 +46,38 @@ def census(preset: str):
 
         step()  # (first step: lazy buffers, merged parameters)
         torch.cuda.synchronize()
-        count("_call", kern._call, lambda name, *a: name.replace("cenet_", ""))
-        count("gemm", kern.gemm, lambda *a, **k: "gemm")
-        count("diffattn_heads", kern.diffattn_heads, lambda a, backward=False: f"dattn_pairs_{'bwd' if backward else 'fwd'}_hd{a.hd}")
-        count("attn64", kern.attn64, lambda a, backward=False: f"attn64_{'bwd' if backward else 'fwd'}")
-        count("flash_fwd", kern.flash_fwd, lambda a, bf=False: "flash_fwd")
-        count("flash_bwd", kern.flash_bwd, lambda a, bf=False: "flash_bwd")
-        count("sra_attn_bwd", kern.sra_attn_bwd, lambda *a, **k: "sra_bwd_resident")
-        step()
-        torch.cuda.synchronize()
+        yield step
     finally:
-        for name, fn in saved.items():
-            setattr(kern, name, fn)
         kern.set_compute_bf16(old)
+
+
+def census(preset: str):
+    from cenet_amd import kern
+    counts = collections.Counter()
+    saved = {}
+
+    def count(name, fn, label):
+        saved[name] = fn
+
+        def f(*a, **k):
+            counts[label(*a, **k)] += 1
+            return fn(*a, **k)
+        setattr(kern, name, f)
+
+    with warm_step(preset) as step:
+        try:
+            count("_call", kern._call, lambda name, *a: name.replace("cenet_", ""))
+            count("gemm", kern.gemm, lambda *a, **k: "gemm")
+            count("diffattn_heads", kern.diffattn_heads, lambda a, backward=False: f"dattn_pairs_{'bwd' if backward else 'fwd'}_hd{a.hd}")
+            count("attn64", kern.attn64, lambda a, backward=False: f"attn64_{'bwd' if backward else 'fwd'}")
+            count("flash_fwd", kern.flash_fwd, lambda a, bf=False: "flash_fwd")
+            count("flash_bwd", kern.flash_bwd, lambda a, bf=False: "flash_bwd")
+            count("sra_attn_bwd", kern.sra_attn_bwd, lambda *a, **k: "sra_bwd_resident")
+            step()
+            torch.cuda.synchronize()
+        finally:
+            for name, fn in saved.items():
+                setattr(kern, name, fn)
     return counts
 
 
