@@ -224,6 +224,10 @@ int cenet_zero_async(float* p, long n, hipStream_t stream);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// host dispatchers of conv_direct.hip / conv_c1.hip / dwconv.hip record the kernel they launch and what selects the code path
+// inside it (printf format); read back by cenet_conv_last_kernel().  Defined in conv_direct.hip.
+void cenet_conv_note(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+
 // q / n without the ~40-instruction integer division, for 0 <= q < 2^20 (exact there: (q + 0.5) / n is at least 0.5 / n away from
 // an integer, the float product's error is below that); inv = cenet_inv_small(n, bound on q), 0 -> the integer division
 static inline float cenet_inv_small_host(int n, long qmax) { return (n > 0 && qmax < (1L << 20)) ? 1.f / (float)n : 0.f; }

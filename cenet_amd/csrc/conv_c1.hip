@@ -335,10 +335,12 @@ extern "C" int cenet_conv_c1_fwd_bf16(const bf16_t* x, const float* w, bf16_t* y
   const dim3 grid(cdiv(W, 128), cdiv(H, 8), B);
   static const bool no_mfma = getenv("CENET_C1_NO_MFMA") != nullptr;  // measurement aid
   if (k == 5 && (W & 15) == 0 && !no_mfma && ((uintptr_t)y & 7) == 0) {
+    cenet_conv_note("conv_c1_fwd_mfma5_kernel rows_per_wg=8");
     CENET_LAUNCH(conv_c1_fwd_mfma5_kernel, grid, dim3(256), stream, a);
     CENET_CHECK_LAUNCH();
     return CENET_OK;
   }
+  cenet_conv_note("conv_c1_fwd_kernel<%d> rows_per_wg=8", k);
   if (k == 1) CENET_LAUNCH((conv_c1_fwd_kernel<1>), grid, dim3(256), stream, a);
   else if (k == 3) CENET_LAUNCH((conv_c1_fwd_kernel<3>), grid, dim3(256), stream, a);
   else CENET_LAUNCH((conv_c1_fwd_kernel<5>), grid, dim3(256), stream, a);
@@ -353,7 +355,7 @@ extern "C" int cenet_conv_c1_wgrad_bf16(const bf16_t* x, const bf16_t* dy, float
   ConvC1Args a;
   a.x = x; a.dy = dy; a.w = nullptr; a.y = nullptr; a.dw = dw_acc; a.B = B; a.Cout = Cout; a.H = H; a.W = W;
   // ~1024 workgroups: enough rows per workgroup to amortise the fold (hundreds of shuffles) and keep the atomics few
-  static const char* e = getenv("CENET_C1_WGS");  // measurement aid
+  const char* e = getenv("CENET_C1_WGS");  // measurement and test aid (read per call)
   const long target = e ? atol(e) : (k >= 3 ? 512 : 1024);  // measured at 224x224, B = 32: 5x5 105 us at 512 (128 at 1024)
   int rows = 8;
   while (rows < H && (long)cdiv(W, 128) * cdiv(H, rows) * B > target) rows += 8;
@@ -361,10 +363,12 @@ extern "C" int cenet_conv_c1_wgrad_bf16(const bf16_t* x, const bf16_t* dy, float
   const dim3 grid(cdiv(W, 128), cdiv(H, rows), B);
   static const bool no_mfma = getenv("CENET_C1_NO_MFMA") != nullptr;  // measurement aid
   if (k == 5 && (W & 31) == 0 && !no_mfma && ((uintptr_t)dy & 15) == 0) {
+    cenet_conv_note("conv_c1_wgrad_mfma5_kernel rows_per_wg=%d", rows);
     CENET_LAUNCH(conv_c1_wgrad_mfma5_kernel, grid, dim3(256), stream, a);
     CENET_CHECK_LAUNCH();
     return CENET_OK;
   }
+  cenet_conv_note("conv_c1_wgrad_kernel<%d> rows_per_wg=%d", k, rows);
   if (k == 1) CENET_LAUNCH((conv_c1_wgrad_kernel<1>), grid, dim3(256), stream, a);
   else if (k == 3) CENET_LAUNCH((conv_c1_wgrad_kernel<3>), grid, dim3(256), stream, a);
   else CENET_LAUNCH((conv_c1_wgrad_kernel<5>), grid, dim3(256), stream, a);
@@ -454,6 +458,7 @@ extern "C" int cenet_pw_small_bf16(const bf16_t* x, const bf16_t* W, bf16_t* y, 
   if (!cenet_pw_small_supported(G) || (long)B * groups > 65535) return CENET_EUNSUPPORTED;
   if ((((uintptr_t)x | (uintptr_t)y) & 3) != 0) return CENET_EINVAL;
   const dim3 grid(cdiv((int)((HW + 1) / 2), 256), B * groups);
+  cenet_conv_note("pw_small_kernel<%d, %s> even=%d", G, transpose ? "true" : "false", (int)((HW & 1) == 0));
 #define PW_GO(G_)                                                                                              \
   do {                                                                                                         \
     if (transpose) CENET_LAUNCH((pw_small_kernel<G_, true>), grid, dim3(256), stream, x, W, y, groups, (int)HW); \
@@ -618,6 +623,7 @@ extern "C" int cenet_pw_fewout_fwd_bf16(const bf16_t* x, const bf16_t* W, const 
   if (!x || !W || !y || B <= 0 || HW <= 0 || HW > 0x7FFFFFFF || B > 65535) return CENET_EINVAL;
   if (!cenet_pw_fewout_supported(Cin, Cout)) return CENET_EUNSUPPORTED;
   if ((((uintptr_t)x | (uintptr_t)y) & 3) != 0) return CENET_EINVAL;
+  cenet_conv_note("pw_fewout_fwd_kernel CO=%d even=%d", Cout, (int)((HW & 1) == 0));
   CENET_LAUNCH(pw_fewout_fwd_kernel, dim3(cdiv((int)((HW + 1) / 2), 256), B), dim3(256), stream, x, W, bias, y, Cout, (int)HW);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
@@ -629,6 +635,7 @@ extern "C" int cenet_pw_fewout_dgrad_bf16(const bf16_t* dy, const bf16_t* W, bf1
   if (!cenet_pw_fewout_supported(Cin, Cout)) return CENET_EUNSUPPORTED;
   if ((((uintptr_t)dy | (uintptr_t)dx) & 3) != 0) return CENET_EINVAL;
   const dim3 grid(cdiv((int)((HW + 1) / 2), 256), B);
+  cenet_conv_note("pw_fewout_dgrad_kernel<%d> even=%d", Cout <= 2 ? 2 : (Cout <= 4 ? 4 : (Cout <= 9 ? 9 : 16)), (int)((HW & 1) == 0));
   if (Cout <= 2) CENET_LAUNCH((pw_fewout_dgrad_kernel<2>), grid, dim3(256), stream, dy, W, dx, Cout, (int)HW);
   else if (Cout <= 4) CENET_LAUNCH((pw_fewout_dgrad_kernel<4>), grid, dim3(256), stream, dy, W, dx, Cout, (int)HW);
   else if (Cout <= 9) CENET_LAUNCH((pw_fewout_dgrad_kernel<9>), grid, dim3(256), stream, dy, W, dx, Cout, (int)HW);
@@ -643,6 +650,7 @@ extern "C" int cenet_pw_fewout_wgrad_bf16(const bf16_t* x, const bf16_t* dy, flo
   if (!cenet_pw_fewout_wgrad_supported(Cin, Cout)) return CENET_EUNSUPPORTED;
   if ((((uintptr_t)x | (uintptr_t)dy) & 3) != 0) return CENET_EINVAL;
   const dim3 grid(cdiv((int)HW, 1024), B);
+  cenet_conv_note("pw_fewout_wgrad_kernel<%d> even=%d", Cout, (int)((HW & 1) == 0));
   if (Cout == 2) CENET_LAUNCH((pw_fewout_wgrad_kernel<2>), grid, dim3(256), stream, x, dy, dW_acc, dbias_acc, (int)HW);
   else if (Cout == 4) CENET_LAUNCH((pw_fewout_wgrad_kernel<4>), grid, dim3(256), stream, x, dy, dW_acc, dbias_acc, (int)HW);
   else CENET_LAUNCH((pw_fewout_wgrad_kernel<9>), grid, dim3(256), stream, x, dy, dW_acc, dbias_acc, (int)HW);

@@ -17,7 +17,20 @@
 // fp32 master copy (a few KB per launch) and rounded once per workgroup; fp32 accumulate.  fp32 tensors (parity mode) take
 // the exact implicit-GEMM path of gemm_core.h instead.
 #include "common.h"
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
 #include "../../include/cenet_hip.h"
+
+// what the last dispatcher call of conv_direct.hip / conv_c1.hip / dwconv.hip on this thread launched (cenet_hip.h)
+static thread_local char g_last_conv_kernel[160] = "";
+extern "C" const char* cenet_conv_last_kernel(void) { return g_last_conv_kernel; }
+void cenet_conv_note(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_last_conv_kernel, sizeof g_last_conv_kernel, fmt, ap);
+  va_end(ap);
+}
 
 #define TH 8
 #define TW 32
@@ -197,6 +210,12 @@ extern "C" int cenet_conv_direct_bf16(const bf16_t* x, const float* w, bf16_t* y
   const bool two = !(k == 3 && Cin == 64 && Cout == 64);
   const int slots = two ? 512 : 256;
   int grid = a.ntiles < slots ? a.ntiles : slots;
+  if (const char* e = getenv("CENET_CONV_DIRECT_GRID")) {  // test aid: few workgroups, so that each one walks several tiles
+    const int gset = atoi(e);
+    if (gset >= 1 && gset < grid) grid = gset;
+  }
+  cenet_conv_note("conv_direct_bf16_kernel<%d, %d, %d, %d> dgrad=%d grid=%d ntiles=%d", Cin, Cout, k,
+                  (Cin == 64 && k == 3) ? 8 : 4, dgrad ? 1 : 0, grid, a.ntiles);
   if (k == 5 && Cin == 32 && Cout == 32) {
     CENET_LAUNCH((conv_direct_bf16_kernel<32, 32, 5, 4>), dim3(grid), dim3(256), stream, a);
   } else if (k == 3 && Cin == 64 && Cout == 64) {
@@ -507,6 +526,8 @@ extern "C" int cenet_conv_wgrad_direct_bf16(const bf16_t* x, const bf16_t* dy, f
   }
   const bool wide = k == 3 && Cout == 64;  // eight waves, one workgroup per CU
   if (wide && grid > CENET_WGRAD_SLABS / 2) grid = CENET_WGRAD_SLABS / 2;
+  cenet_conv_note("conv_wgrad_direct_kernel<%s> vec=%d grid=%d ntiles=%d",
+                  k == 5 ? "32, 32, 5, 8, 8, 2" : (wide ? "64, 64, 3, 4, 8" : "64, 32, 3, 4, 4"), a.vec, grid, a.ntiles);
   if (k == 5) CENET_LAUNCH((conv_wgrad_direct_kernel<32, 32, 5, 8, 8, 2>), dim3(grid), dim3(512), stream, a);
   else if (wide) CENET_LAUNCH((conv_wgrad_direct_kernel<64, 64, 3, 4, 8>), dim3(grid), dim3(512), stream, a);
   else CENET_LAUNCH((conv_wgrad_direct_kernel<64, 32, 3, 4, 4>), dim3(grid), dim3(256), stream, a);

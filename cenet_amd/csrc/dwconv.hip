@@ -6,6 +6,7 @@
 // token-layout threads run along C.  The data-gradient is the same kernel with the 3x3 taps flipped.
 // Templates over the activation storage type T (float / bf16_t, common.h); weights, bias and their gradients are fp32.
 #include "common.h"
+#include <cstdio>
 #include <cstdlib>
 #include "../../include/cenet_hip.h"
 
@@ -409,6 +410,11 @@ static inline bool al16p(const void* a, const void* b, const void* c) {
   return ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & (4 * sizeof(T) - 1)) == 0);
 }
 
+// how the reporter (cenet_conv_note) spells the ACT template argument and the storage type
+static inline const char* dw_act_name(bool none, int act) { return none ? "ACT_NONE" : (act == ACT_GELU ? "ACT_GELU" : "-1"); }
+template <typename T>
+static inline const char* dw_type_name() { return sizeof(T) == 2 ? "bf16_t" : "float"; }
+
 static inline int plane_chunks(int HW) {
   int ch = cdiv(HW, 1024);
   return ch > 64 ? 64 : ch;
@@ -742,6 +748,7 @@ static int dwconv3x3_nchw_impl(const T* x, long sxb, const float* w, const float
       p.dy = nullptr; p.sgb = 0; p.dw = p.db = nullptr;
       p.BC = B * C; p.C = C; p.H = H; p.W = W; p.dil = dil; p.flip = flip; p.act = act; p.ppw = ppw; p.slope = slope;
       const dim3 grid(cdiv(B * C, ppw));
+      cenet_conv_note("dw3x3_nchw_plane_kernel<%s> ppw=%d", dw_act_name(!a || act == ACT_NONE, act), ppw);
       if (!a || act == ACT_NONE) CENET_LAUNCH((dw3x3_nchw_plane_kernel<ACT_NONE>), grid, dim3(256), stream, p);
       else if (act == ACT_GELU) CENET_LAUNCH((dw3x3_nchw_plane_kernel<ACT_GELU>), grid, dim3(256), stream, p);
       else CENET_LAUNCH((dw3x3_nchw_plane_kernel<-1>), grid, dim3(256), stream, p);
@@ -754,6 +761,8 @@ static int dwconv3x3_nchw_impl(const T* x, long sxb, const float* w, const float
     const int th = nq <= 64 ? 64 : (nq <= 128 ? 128 : 256);
     int ch = cdiv(nq, th * 2);
     if (ch > 16) ch = 16;
+    cenet_conv_note("dw3x3_nchw_v4_kernel<%s, %s>", dw_type_name<T>(),
+                    sizeof(T) == 2 ? dw_act_name(!a || act == ACT_NONE, act) : "-1");
     if (sizeof(T) == 2 && (!a || act == ACT_NONE))
       CENET_LAUNCH((dw3x3_nchw_v4_kernel<T, ACT_NONE>), dim3(B * C, ch), dim3(th), stream, x, sxb, w, bias, y, syb, a, sab, C, H, W,
                    dil, flip, act, slope);
@@ -764,6 +773,7 @@ static int dwconv3x3_nchw_impl(const T* x, long sxb, const float* w, const float
       CENET_LAUNCH((dw3x3_nchw_v4_kernel<T, -1>), dim3(B * C, ch), dim3(th), stream, x, sxb, w, bias, y, syb, a, sab, C, H, W, dil,
                    flip, act, slope);
   } else {
+    cenet_conv_note("dw3x3_nchw_kernel<%s>", dw_type_name<T>());
     CENET_LAUNCH((dw3x3_nchw_kernel<T>), dim3(B * C, plane_chunks(H * W)), dim3(256), stream, x, sxb, w, bias, y, syb, a, sab, C,
                  H, W, dil, flip, act, slope);
   }
@@ -1142,6 +1152,7 @@ __global__ __launch_bounds__(HW == 14 ? 448 : 256, HW == 14 ? 4 : 3) void dw3x3_
 template <int HW, int MODE>
 static void dw_plane_go(const DwTileArgs& a, int B, hipStream_t stream) {
   const dim3 grid(a.C / 64, B), block(HW == 14 ? 448 : 256);
+  cenet_conv_note("dw3x3_tok_plane_kernel<%d, %d, %s>", HW, MODE, dw_act_name(MODE == 1 || a.act == ACT_NONE, a.act));
   if (MODE == 1 || a.act == ACT_NONE) CENET_LAUNCH((dw3x3_tok_plane_kernel<HW, MODE, ACT_NONE>), grid, block, stream, a);
   else if (a.act == ACT_GELU) CENET_LAUNCH((dw3x3_tok_plane_kernel<HW, MODE, ACT_GELU>), grid, block, stream, a);
   else CENET_LAUNCH((dw3x3_tok_plane_kernel<HW, MODE, -1>), grid, block, stream, a);
@@ -1157,12 +1168,14 @@ static int dw_tile_launch(DwTileArgs a, int B, hipStream_t stream) {
     a.ntiles = a.tiles_x * cdiv(a.H, TH_);                                                                       \
     a.tpw = 1;                                                                                                   \
     if (MODE == 2) {                                                                                             \
-      static const char* e = getenv("CENET_DW_TPW");                                                              \
+      const char* e = getenv("CENET_DW_TPW"); /* measurement and test aid (read per call) */                     \
       a.tpw = e ? atoi(e) : (a.ntiles >= 16 ? 2 : 1); /* measured: more tiles per workgroup only cost parallelism */                                      \
       if (a.tpw > a.ntiles) a.tpw = a.ntiles;                                                                    \
     }                                                                                                            \
     const dim3 grid(slabs, cdiv(a.ntiles, a.tpw), B);                                                            \
     if (grid.y > 65535 || grid.z > 65535) return CENET_EUNSUPPORTED;                                             \
+    cenet_conv_note("dw3x3_tok_tile_kernel<%d, %d, %d, %s> tpw=%d", TH_, TW_, MODE,                               \
+                    dw_act_name(MODE == 1 || a.act == ACT_NONE, a.act), a.tpw);                                   \
     if (MODE == 1 || a.act == ACT_NONE)                                                                          \
       CENET_LAUNCH((dw3x3_tok_tile_kernel<TH_, TW_, MODE, ACT_NONE>), grid, dim3(256), stream, a);               \
     else if (a.act == ACT_GELU)                                                                                  \
@@ -1218,6 +1231,7 @@ static int dwconv3x3_tok_impl(const T* x, const float* w, const float* bias, T* 
   // bf16: two channels per thread (4-byte accesses) when C is even and the tensors are 4-byte aligned
   constexpr int CP2 = sizeof(T) == 2 ? 2 : 1;
   const bool two = CP2 == 2 && (C & 1) == 0 && ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)a) & 3) == 0);
+  cenet_conv_note("dw3x3_tok_kernel<%s, %d, %d>", dw_type_name<T>(), sr, two ? 2 : 1);
   if (two) {
     const dim3 grid(cdiv(C, 512), strips, B);
     if (sr == 4) CENET_LAUNCH((dw3x3_tok_kernel<T, 4, CP2>), grid, dim3(256), stream, x, w, bias, y, a, C, H, W, flip, act, slope);
@@ -1358,11 +1372,13 @@ static int dwconv3x3_wgrad_nchw_acc_impl(const T* x, long sxb, const T* dy, long
         if (ng < 1) ng = 1;
         if (ng > cdiv(B, np)) ng = cdiv(B, np);
         const int ipg = cdiv(cdiv(B, ng), np) * np;  // whole passes per group
+        cenet_conv_note("dw3x3_wgrad_nchw_chan_kernel<%s> np=%d ipg=%d groups=%d", dil == 1 ? "true" : "false", np, ipg, cdiv(B, ipg));
         if (dil == 1) CENET_LAUNCH(dw3x3_wgrad_nchw_chan_kernel<true>, dim3(C, cdiv(B, ipg)), dim3(256), stream, p, B, ipg, np);
         else CENET_LAUNCH(dw3x3_wgrad_nchw_chan_kernel<false>, dim3(C, cdiv(B, ipg)), dim3(256), stream, p, B, ipg, np);
         CENET_CHECK_LAUNCH();
         return CENET_OK;
       }
+      cenet_conv_note("dw3x3_wgrad_nchw_plane_kernel ppw=%d", ppw);
       CENET_LAUNCH(dw3x3_wgrad_nchw_plane_kernel, dim3(cdiv(B * C, ppw)), dim3(256), stream, p);
       CENET_CHECK_LAUNCH();
       return CENET_OK;
@@ -1379,9 +1395,11 @@ static int dwconv3x3_wgrad_nchw_acc_impl(const T* x, long sxb, const T* dy, long
     if (w4 > m4) w4 = m4;
     if (w4 < 1) w4 = 1;
     if (w4 > 256) w4 = 256;
+    cenet_conv_note("dw3x3_wgrad_nchw_v4_kernel<%s>", dw_type_name<T>());
     CENET_LAUNCH((dw3x3_wgrad_nchw_v4_kernel<T>), dim3(C, (unsigned)w4), dim3(256), stream, x, sxb, dy, sgb, dw_acc, dbias_acc,
                  B, C, H, W, dil);
   } else {
+    cenet_conv_note("dw3x3_wgrad_nchw_kernel<%s>", dw_type_name<T>());
     CENET_LAUNCH((dw3x3_wgrad_nchw_kernel<T>), dim3(C, (unsigned)want), dim3(256), stream, x, sxb, dy, sgb, dw_acc, dbias_acc, B,
                  C, H, W, dil);
   }
@@ -1415,6 +1433,12 @@ extern "C" int cenet_dwconv3x3_nchw_multi_bf16(const bf16_t* const* x, const lon
     if (g > gx) gx = g;
   }
   for (int i = n; i < DWP_MULTI_MAX; ++i) m.a[i] = m.a[0];
+  {
+    char pp[64];
+    int len = 0;
+    for (int i = 0; i < n; ++i) len += snprintf(pp + len, sizeof pp - len, i ? ",%d" : "%d", m.a[i].ppw);
+    cenet_conv_note("dw3x3_nchw_plane_multi_kernel ppw=%s", pp);
+  }
   CENET_LAUNCH(dw3x3_nchw_plane_multi_kernel, dim3(gx, n), dim3(256), stream, m);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
@@ -1441,6 +1465,12 @@ extern "C" int cenet_dwconv3x3_wgrad_nchw_multi_bf16(const bf16_t* const* x, con
     if (g > gx) gx = g;
   }
   for (int i = n; i < DWP_MULTI_MAX; ++i) m.a[i] = m.a[0];
+  {
+    char pp[64];
+    int len = 0;
+    for (int i = 0; i < n; ++i) len += snprintf(pp + len, sizeof pp - len, i ? ",%d" : "%d", m.a[i].ppw);
+    cenet_conv_note("dw3x3_wgrad_nchw_plane_multi_kernel ppw=%s", pp);
+  }
   CENET_LAUNCH(dw3x3_wgrad_nchw_plane_multi_kernel, dim3(gx, n), dim3(256), stream, m);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
@@ -1451,9 +1481,11 @@ static int dwconv3x3_wgrad_tok_acc_impl(const T* x, const T* dy, float* dw_acc, 
                                         hipStream_t stream) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return CENET_EINVAL;
   if ((C & 3) == 0 && al16p<T>(x, dy, nullptr)) {
+    cenet_conv_note("dw3x3_wgrad_tok_v4_kernel<%s>", dw_type_name<T>());
     CENET_LAUNCH((dw3x3_wgrad_tok_v4_kernel<T>), dim3(cdiv(C, 256), cdiv(H, 4), B), dim3(256), stream, x, dy, dw_acc, dbias_acc,
                  C, H, W);
   } else {
+    cenet_conv_note("dw3x3_wgrad_tok_kernel<%s>", dw_type_name<T>());
     CENET_LAUNCH((dw3x3_wgrad_tok_kernel<T>), dim3(cdiv(C, 256), cdiv(H, DW_WROWS), B), dim3(256), stream, x, dy, dw_acc,
                  dbias_acc, C, H, W);
   }

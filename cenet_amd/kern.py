@@ -188,6 +188,14 @@ def last_gemm_kernel() -> str:
     return f().decode()
 
 
+def last_conv_kernel() -> str:
+    """what the last call on this thread into conv_direct.hip / conv_c1.hip / dwconv.hip launched: the kernel with its template
+    arguments and the run-time numbers that pick a code path inside it (cenet_conv_last_kernel); test and measurement aid"""
+    f = _lib.lib().cenet_conv_last_kernel
+    f.restype = C.c_char_p
+    return f().decode()
+
+
 # ------------------------------------------------------------------------------------------------
 # generic call helper
 # ------------------------------------------------------------------------------------------------

@@ -154,6 +154,10 @@ int cenet_conv_wgrad_direct_supported(int Cin, int Cout, int k, int stride, int 
 long cenet_conv_wgrad_direct_ws_floats(int Cin, int Cout, int k);
 int cenet_conv_wgrad_direct_bf16(const unsigned short* x, const unsigned short* dy, float* dw_acc, float* ws, int B, int Cin,
                                  int Cout, int H, int W, int k, cenet_stream_t stream);
+/* Test and measurement aid: what the last call on this thread into conv_direct.hip, conv_c1.hip or dwconv.hip launched — the kernel
+ * with its template arguments, then the run-time numbers that select a code path inside it ("conv_direct_bf16_kernel<32, 32, 5, 4>
+ * dgrad=0 grid=5 ntiles=24", "dw3x3_nchw_plane_kernel<ACT_GELU> ppw=4").  Written by the host dispatchers only. */
+const char* cenet_conv_last_kernel(void);
 
 /* ---- attention (attn.hip) -------------------------------------------------------------------------------- */
 /* Element (b,h,i,d) of Q = q[b*qsb + h*qsh + i*qsi + d*qsd]; same for K (Nk rows), V (head h / v_head_div,

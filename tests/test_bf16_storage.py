@@ -130,7 +130,8 @@ def test_conv2d_implicit_gemm(dev, Cin, Cout, k, s, H, expand, layout):
 
 
 # the one-channel stencils of conv_c1.hip (bf16 only; fp32 takes the implicit GEMM): k = 5 / 3 / 1, full 128-column tiles with
-# a ragged last one (W = 140), a width that is not a multiple of 4 (scalar stores), several row groups per workgroup.  The
+# a ragged last one (W = 140), a width that is not a multiple of 4 (scalar stores); every shape here stays at rows_per_wg = 8 (the
+# longer row groups of the weight gradient are reached in tests/test_conv_bounds.py through CENET_C1_WGS).  The
 # input needs no gradient in the network; here x does, which exercises the generic data-gradient path behind the special forward.
 # W % 32 == 0 with k = 5: the matrix-core kernels (taps as the contraction / an output dimension); 160 columns = a full and a
 # quarter tile, 19 rows = ragged row groups, 24 channels = a partly empty second channel fragment
@@ -207,8 +208,9 @@ def test_dwconv_tok(dev, B, C, H, W, act):
     compare(lambda x, w, b: ops.dwconv_tok(x, w, b, H, W, act), [x], [w, b], dev=dev)
 
 
-# bf16 with H*W % 4 == 0 takes the plane-in-LDS kernels (several planes per workgroup; 14x14: quads straddle rows; dilation 5;
-# 7x7 keeps the scalar kernels); the 2 x 70 x 8 x 8 case makes a workgroup's planes span two images
+# bf16 with H*W % 4 == 0 takes the plane-in-LDS kernels (14x14: quads straddle rows; dilation 5; 7x7 keeps the scalar kernels).
+# Every shape here runs ONE plane per workgroup (dwp_ppw stays 1 below B C = 2047); several planes per workgroup, and a workgroup
+# whose planes span two images, are reached in tests/test_conv_bounds.py (2 x 2050 x 4 x 4, ppw = 4, asserted through the reporter)
 @pytest.mark.parametrize("B,C,H,W,dil,act", [(2, 3, 8, 8, 1, "gelu"), (1, 2, 12, 12, 2, "none"), (2, 3, 7, 7, 3, "none"),
                                              (2, 5, 14, 14, 1, "gelu"), (1, 3, 20, 28, 5, "none"), (2, 70, 8, 8, 2, "none"),
                                              # one plane per workgroup (owned quads; the weight gradient's workgroup reduction)
