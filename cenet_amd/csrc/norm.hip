@@ -2,11 +2,31 @@
 //   LayerNorm : pvtv2.py:117,124,166,69,221-245 (eps 1e-6 in blocks, 1e-5 in patch-embed / sr norm)
 //   BatchNorm : cfam.py:22-32, blocks.py:151,161,212,307, nlb.py:81, unet.py:175-197, cfam.py:92,250
 // Kernels are templates over the activation storage type T (float / bf16_t, common.h); gamma / beta / statistics / parameter
-// gradients are fp32.  All statistics in fp32; BN batch statistics use per-channel shifted sums (shift = first element) so that
-// E[x^2]-E[x]^2 does not cancel; partial sums from several workgroups per channel meet in float atomics.
+// gradients are fp32.  All statistics in fp32; BN batch statistics use per-channel shifted sums so that E[x^2]-E[x]^2 does not
+// cancel: the shift is the mean of the first min(HW, 64) elements of image 0's plane (bn_shift_block; NOT one element: a single
+// zero in front of a channel at 8 +- 0.03 costs the variance up to 7e-4 of its value), computed by the producer of the partial sums and
+// handed to their consumer through the workspace; partial sums of several workgroups per channel lie in one slot each.
 #include "common.h"
+#include <cstdarg>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include "../../include/cenet_hip.h"
+
+// what the last dispatcher call of this file on this thread launched (cenet_hip.h): host only, no effect on a launch
+static thread_local char g_last_norm_kernel[256] = "";
+extern "C" const char* cenet_norm_last_kernel(void) { return g_last_norm_kernel; }
+// cont: a further launch of the same call ("a+b")
+__attribute__((format(printf, 2, 3))) static void norm_note(bool cont, const char* fmt, ...) {
+  size_t at = cont ? strlen(g_last_norm_kernel) : 0;
+  if (at && at + 1 < sizeof g_last_norm_kernel) g_last_norm_kernel[at++] = '+';
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_last_norm_kernel + at, sizeof g_last_norm_kernel - at, fmt, ap);
+  va_end(ap);
+}
+template <typename T>
+static inline const char* norm_tn() { return sizeof(T) == 2 ? "bf16_t" : "float"; }
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm: one wave per row, 4 rows per 256-thread workgroup.
@@ -451,6 +471,7 @@ extern "C" int cenet_layernorm_fwd_acc_bf16(float* acc, const float* bias, bf16_
       ((((uintptr_t)acc | (uintptr_t)bias | (uintptr_t)gamma | (uintptr_t)beta) & 15) != 0) ||
       ((((uintptr_t)xpre | (uintptr_t)y) & 7) != 0))
     return CENET_EUNSUPPORTED;
+  norm_note(false, "ln_fwd_acc_kernel");
   CENET_LAUNCH(ln_fwd_acc_kernel, dim3(cdiv(rows, 4)), dim3(256), stream, acc, bias, xpre, gamma, beta, y, mean, rstd, rows, C, eps);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
@@ -525,6 +546,7 @@ extern "C" int cenet_layernorm_bwd_add_part_scaled_bf16(const bf16_t* dy, const 
 #define CENET_LNP8(LPRv)                                                                                               \
   {                                                                                                                   \
     const int rps = 4 * 64 / LPRv, st = ln_steps(rows, rps, 1024);                                                    \
+    norm_note(false, "ln_bwd_v8_kernel<%d, 1> part dxs=%d steps=%d", LPRv, dxs != nullptr, st);                         \
     CENET_LAUNCH((ln_bwd_v8_kernel<LPRv, 1>), dim3(cdiv(rows, rps * st)), dim3(256), stream, dy, x, gamma, mean, rstd, dx, \
                  (float*)nullptr, (float*)nullptr, rows, C, st, dx_add, part, bscale, rows_per_sample, dxs);            \
   }
@@ -551,6 +573,7 @@ extern "C" int cenet_ln_fold_group(const void* const* part, float* const* dg, fl
   if (n < 0 || (n > 0 && (!part || !dg || !db || !nrows || !C))) return CENET_EINVAL;
   for (int i = 0; i < n; ++i)
     if (!part[i] || !dg[i] || !db[i] || nrows[i] <= 0 || C[i] <= 0) return CENET_EINVAL;
+  g_last_norm_kernel[0] = 0;
   int i = 0;
   while (i < n) {
     LnFoldArgs a;
@@ -565,6 +588,7 @@ extern "C" int cenet_ln_fold_group(const void* const* part, float* const* dg, fl
       if (C[i] > cmax) cmax = C[i];
       ++m;
     }
+    norm_note(i > m, "ln_fold_group_kernel items=%d", m);
     CENET_LAUNCH(ln_fold_group_kernel, dim3(cdiv(2 * cmax, 32), m), dim3(1024), stream, a);
     CENET_CHECK_LAUNCH();
   }
@@ -597,6 +621,7 @@ static int layernorm_fwd_impl(const T* x, const float* gamma, const float* beta,
 #define CENET_LNF(LPRv, NPv)                                                                                          \
   {                                                                                                                   \
     const int rps = 4 * 64 / LPRv, st = ln_steps(rows, rps, 1024);                                                          \
+    norm_note(false, "ln_fwd_v4_kernel<%s, %d, %d> steps=%d", norm_tn<T>(), LPRv, NPv, st);                                  \
     CENET_LAUNCH((ln_fwd_v4_kernel<T, LPRv, NPv>), dim3(cdiv(rows, rps * st)), dim3(256), stream, x, gamma, beta, y, mean, rstd, \
                  rows, C, eps, st);                                                                                   \
   }
@@ -606,6 +631,7 @@ static int layernorm_fwd_impl(const T* x, const float* gamma, const float* beta,
     else CENET_LNF(64, 2)
 #undef CENET_LNF
   } else {
+    norm_note(false, "layernorm_fwd_kernel<%s>", norm_tn<T>());
     CENET_LAUNCH((layernorm_fwd_kernel<T>), dim3(cdiv(rows, 4)), dim3(256), stream, x, gamma, beta, y, mean, rstd, rows, C, eps);
   }
   CENET_CHECK_LAUNCH();
@@ -625,6 +651,7 @@ static int layernorm_bwd_add_acc_impl(const T* dy, const T* x, const float* gamm
 #define CENET_LNB8(LPRv, NPv)                                                                                         \
   {                                                                                                                   \
     const int rps = 4 * 64 / LPRv, st = ln_steps(rows, rps, 256);                                                     \
+    norm_note(false, "ln_bwd_v8_kernel<%d, %d> steps=%d", LPRv, NPv, st);                                              \
     CENET_LAUNCH((ln_bwd_v8_kernel<LPRv, NPv>), dim3(cdiv(rows, rps * st)), dim3(256), stream, (const bf16_t*)dy,      \
                  (const bf16_t*)x, gamma, mean, rstd, (bf16_t*)dx, dgamma_acc, dbeta_acc, rows, C, st, (const bf16_t*)dx_add, (float*)nullptr, \
                  (const float*)nullptr, 1, (bf16_t*)nullptr); \
@@ -641,6 +668,7 @@ static int layernorm_bwd_add_acc_impl(const T* dy, const T* x, const float* gamm
 #define CENET_LNB(LPRv, NPv)                                                                                          \
   {                                                                                                                   \
     const int rps = 4 * 64 / LPRv, st = ln_steps(rows, rps, sizeof(T) == 2 ? 256 : 1024);                             \
+    norm_note(false, "ln_bwd_v4_kernel<%s, %d, %d> steps=%d", norm_tn<T>(), LPRv, NPv, st);                            \
     CENET_LAUNCH((ln_bwd_v4_kernel<T, LPRv, NPv>), dim3(cdiv(rows, rps * st)), dim3(256), stream, dy, x, gamma, mean, rstd, dx, \
                  dgamma_acc, dbeta_acc, rows, C, st, dx_add);                                                         \
   }
@@ -654,6 +682,7 @@ static int layernorm_bwd_add_acc_impl(const T* dy, const T* x, const float* gamm
   }
   dim3 grid(cdiv(rows, LN_ROWS_PER_BLOCK));
 #define CENET_LN(MJ, RP)                                                                                            \
+  norm_note(false, "layernorm_bwd_kernel<%s, %d, %d>", norm_tn<T>(), MJ, RP);                                        \
   CENET_LAUNCH((layernorm_bwd_kernel<T, MJ, RP>), grid, dim3(256), stream, dy, x, gamma, mean, rstd, dx, dgamma_acc, dbeta_acc, \
                rows, C, dx_add)
   if (C <= 64) { CENET_LN(1, 4); }
@@ -681,13 +710,23 @@ CENET_TWIN(layernorm_bwd_acc, (const T* dy, const T* x, const float* gamma, cons
 // ------------------------------------------------------------------------------------------------
 // BatchNorm (training): statistics over (B, HW) per channel of x[b*sb + c*HW + p].
 // ------------------------------------------------------------------------------------------------
+// The shift of channel c's one-pass sums: the fp32 mean of the first min(HW, 64) elements of image 0's plane (xc), one element per
+// lane of wave 0 (the other waves add exact zeros), so every workgroup of the channel gets the same bits; the workgroup of split 0
+// stores it behind the partial sums, at ws[2 C S + c], where the consumers of the sums read it (BN_SHIFT_AT).  Every thread calls.
+#define BN_SHIFT_AT(C, S, c) (2L * (C) * (S) + (c))
+template <typename T>
+__device__ __forceinline__ float bn_shift_block(const T* __restrict__ xc, int HW, float* red) {
+  const int m = HW < 64 ? HW : 64;
+  return block_sum((int)threadIdx.x < m ? ldf(xc + threadIdx.x) : 0.f, red) / (float)m;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void bn_partial_kernel(const T* __restrict__ x, long sb, int B, int HW,
                                                         float* __restrict__ ws) {
   __shared__ float red[16];
   const int c = blockIdx.x;
   const T* xc = x + (long)c * HW;
-  const float shift = ldf(xc);
+  const float shift = bn_shift_block<T>(xc, HW, red);
   const long total = (long)B * HW;
   float s1 = 0.f, s2 = 0.f;
   for (int w__ = blockIdx.y; w__ < B * ((HW + 1023) / 1024); w__ += gridDim.y)  // (image, 1024-pixel chunk) items: no per-element division
@@ -703,6 +742,7 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const T* __restrict__ x
   if (threadIdx.x == 0) {  // one slot per (channel, split): no zero-fill, no atomics; the consumer adds the gridDim.y slots
     ws[((long)c) * gridDim.y + blockIdx.y] = s1;
     ws[((long)gridDim.x + c) * gridDim.y + blockIdx.y] = s2;
+    if (blockIdx.y == 0) ws[BN_SHIFT_AT(gridDim.x, gridDim.y, c)] = shift;
   }
 }
 
@@ -712,7 +752,7 @@ __global__ void bn_finalize_kernel(const T* __restrict__ x, int HW, const float*
                                    float* running_var, float momentum, long* nbt, int nbt_n) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < C) {
-    float shift = ldf(x + (long)c * HW);
+    float shift = ws[BN_SHIFT_AT(C, S, c)];
     float a1 = 0.f, a2 = 0.f;
     for (int i = 0; i < S; ++i) {
       a1 += ws[(long)c * S + i];
@@ -736,7 +776,7 @@ __global__ void bn_finalize_kernel(const T* __restrict__ x, int HW, const float*
 // variance of its channel from the partial sums itself (what bn_finalize_kernel does), and the workgroup (thread) that handles
 // the first elements of image 0's plane publishes mean / var for the backward pass and updates the running statistics.
 struct BnFin {
-  const float* ws;  // partial sums [2][C][S] of the shifted values (nullptr: mean / var are given)
+  const float* ws;  // partial sums [2][C][S] of the shifted values, then the C shifts (nullptr: mean / var are given)
   int S;
   float n;          // B * HW
   float *mean, *var, *rmean, *rvar;
@@ -766,7 +806,7 @@ __device__ __forceinline__ void bn_fin_plane(const BnFin& f, const T* x, int C, 
   const float m = a1 / f.n;
   v = a2 / f.n - m * m;
   if (v < 0.f) v = 0.f;
-  mu = ldf(x + (long)c * HW) + m;
+  mu = f.ws[BN_SHIFT_AT(C, f.S, c)] + m;
   if (writer && threadIdx.x == 0) bn_fin_publish(f, c, mu, v);
 }
 
@@ -864,7 +904,7 @@ __global__ __launch_bounds__(256) void bn_partial_v4_kernel(const T* __restrict_
   __shared__ float red[16];
   const int c = blockIdx.x, nq = HW >> 2;
   const T* xc = x + (long)c * HW;
-  const float shift = ldf(xc);
+  const float shift = bn_shift_block<T>(xc, HW, red);
   const int total = B * nq, stride = gridDim.y * 256;
   const float inv_nq = cenet_inv_small(nq, total);
   float s1 = 0.f, s2 = 0.f;
@@ -894,6 +934,7 @@ __global__ __launch_bounds__(256) void bn_partial_v4_kernel(const T* __restrict_
   if (threadIdx.x == 0) {  // one slot per (channel, split): no zero-fill, no atomics; the consumer adds the gridDim.y slots
     ws[((long)c) * gridDim.y + blockIdx.y] = s1;
     ws[((long)gridDim.x + c) * gridDim.y + blockIdx.y] = s2;
+    if (blockIdx.y == 0) ws[BN_SHIFT_AT(gridDim.x, gridDim.y, c)] = shift;
   }
 }
 
@@ -1042,7 +1083,7 @@ __global__ __launch_bounds__(256) void bn_apply_flat_kernel(const T* __restrict_
     const float m = a1 / fin.n;
     vr = a2 / fin.n - m * m;
     if (vr < 0.f) vr = 0.f;
-    mu = ldf(x + (long)c * HWv * V) + m;
+    mu = fin.ws[BN_SHIFT_AT(C, fin.S, c)] + m;
     if (plane < C && i == (long)plane * HWv) bn_fin_publish(fin, c, mu, vr);
   } else {
     mu = mean[c], vr = var[c];
@@ -1103,7 +1144,7 @@ __global__ __launch_bounds__(256) void bn_partial_flat_kernel(const T* __restric
   __shared__ float red[16];
   const int c = blockIdx.x;
   const int total = B * HW;
-  const float shift = ldf(x + (long)c * HW);
+  const float shift = bn_shift_block<T>(x + (long)c * HW, HW, red);
   float s1 = 0.f, s2 = 0.f;
   for (int e = blockIdx.y * 256 + threadIdx.x; e < total; e += gridDim.y * 256) {
     const int b = e / HW, p = e - b * HW;
@@ -1116,6 +1157,7 @@ __global__ __launch_bounds__(256) void bn_partial_flat_kernel(const T* __restric
   if (threadIdx.x == 0) {
     ws[((long)c) * gridDim.y + blockIdx.y] = s1;
     ws[((long)gridDim.x + c) * gridDim.y + blockIdx.y] = s2;
+    if (blockIdx.y == 0) ws[BN_SHIFT_AT(gridDim.x, gridDim.y, c)] = shift;
   }
 }
 
@@ -1323,6 +1365,7 @@ extern "C" int cenet_bn1d_train_fwd_f32(const float* z, float* zn, float* mean, 
   if (!z || !zn || !mean || !var || !gamma || !beta || C <= 0 || (running_mean != nullptr) != (running_var != nullptr))
     return CENET_EINVAL;
   if (!cenet_bn1d_supported(B)) return CENET_EUNSUPPORTED;
+  norm_note(false, "bn1d_train_fwd_kernel");
   CENET_LAUNCH(bn1d_train_fwd_kernel, dim3(cdiv(C, 64)), dim3(256), stream, z, zn, mean, var, running_mean, running_var, momentum,
                num_batches_tracked, eps, gamma, beta, B, C);
   CENET_CHECK_LAUNCH();
@@ -1333,6 +1376,7 @@ extern "C" int cenet_bn1d_bwd_acc_f32(const float* dy, const float* z, float* dz
                                       const float* gamma, float* dgamma_acc, float* dbeta_acc, int B, int C, hipStream_t stream) {
   if (!dy || !z || !dz || !mean || !var || !gamma || C <= 0) return CENET_EINVAL;
   if (!cenet_bn1d_supported(B)) return CENET_EUNSUPPORTED;
+  norm_note(false, "bn1d_bwd_kernel");
   CENET_LAUNCH(bn1d_bwd_kernel, dim3(cdiv(C, 64)), dim3(256), stream, dy, z, dz, mean, var, eps, gamma, dgamma_acc, dbeta_acc, B, C);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
@@ -1358,13 +1402,15 @@ static inline void bn_plane_launch(int nq, int* threads, int* chunks) {
   if (ch < 1) ch = 1;
   *chunks = ch;
 }
-// workgroups per channel of the reductions: ~2048 in all, each at least 1024 quads deep
+// workgroups per channel of the reductions: ~2048 in all, each at least 1024 quads deep; at most 255, so that the C shifts fit
+// behind the 2 C S partial sums in the CENET_BN_WS_FLOATS(C) = 2 C 256 floats of the workspace
+#define BN_MAX_SPLITS 255
 static inline int bn_splits_v4(int C, long quads) {
   long want = 2048 / (C > 0 ? C : 1);
   long maxs = (quads + 1023) / 1024;
   if (want > maxs) want = maxs;
   if (want < 1) want = 1;
-  if (want > 256) want = 256;
+  if (want > BN_MAX_SPLITS) want = BN_MAX_SPLITS;
   return (int)want;
 }
 
@@ -1374,7 +1420,7 @@ static inline int bn_splits(int C, long total) {
   if (want < 1) want = 1;
   if (want > maxs) want = maxs;
   if (want < 1) want = 1;
-  if (want > 256) want = 256;
+  if (want > BN_MAX_SPLITS) want = BN_MAX_SPLITS;
   return (int)want;
 }
 
@@ -1384,12 +1430,15 @@ static int bn_partial_launch(const T* x, long sb, int B, int C, int HW, float* w
   int S;
   if (bn_v4_ok<T>(HW, x, sb, x, sb, x, sb)) {
     S = bn_splits_v4(C, total / 4);
+    norm_note(false, "bn_partial_v4_kernel<%s> S=%d", norm_tn<T>(), S);
     CENET_LAUNCH((bn_partial_v4_kernel<T>), dim3(C, S), dim3(256), stream, x, sb, B, HW, ws);
   } else if (sizeof(T) == 2 && HW <= 1024) {
     S = bn_splits(C, total);
+    norm_note(false, "bn_partial_flat_kernel<%s> S=%d", norm_tn<T>(), S);
     CENET_LAUNCH((bn_partial_flat_kernel<T>), dim3(C, S), dim3(256), stream, x, sb, B, HW, ws);
   } else {
     S = bn_splits(C, total);
+    norm_note(false, "bn_partial_kernel<%s> S=%d", norm_tn<T>(), S);
     CENET_LAUNCH((bn_partial_kernel<T>), dim3(C, S), dim3(256), stream, x, sb, B, HW, ws);
   }
   return S;
@@ -1403,14 +1452,18 @@ static int bn_stats_impl(const T* x, long sb, int B, int C, int HW, float* ws, f
   int S;
   if (bn_v4_ok<T>(HW, x, sb, x, sb, x, sb)) {
     S = bn_splits_v4(C, total / 4);
+    norm_note(false, "bn_partial_v4_kernel<%s> S=%d", norm_tn<T>(), S);
     CENET_LAUNCH((bn_partial_v4_kernel<T>), dim3(C, S), dim3(256), stream, x, sb, B, HW, ws);
   } else if (sizeof(T) == 2 && HW <= 1024) {
     S = bn_splits(C, total);
+    norm_note(false, "bn_partial_flat_kernel<%s> S=%d", norm_tn<T>(), S);
     CENET_LAUNCH((bn_partial_flat_kernel<T>), dim3(C, S), dim3(256), stream, x, sb, B, HW, ws);
   } else {
     S = bn_splits(C, total);
+    norm_note(false, "bn_partial_kernel<%s> S=%d", norm_tn<T>(), S);
     CENET_LAUNCH((bn_partial_kernel<T>), dim3(C, S), dim3(256), stream, x, sb, B, HW, ws);
   }
+  norm_note(true, "bn_finalize_kernel<%s>", norm_tn<T>());
   CENET_LAUNCH((bn_finalize_kernel<T>), dim3(cdiv(C, 64)), dim3(64), stream, x, HW, (const float*)ws, C, S, (float)total, mean,
                var, running_mean, running_var, momentum, num_batches_tracked, nbt_count);
   CENET_CHECK_LAUNCH();
@@ -1423,14 +1476,16 @@ CENET_TWIN(bn_stats, (const T* x, long sb, int B, int C, int HW, float* ws, floa
 template <typename T>
 static int bn_apply_launch(const T* x, long sxb, T* y, long syb, const float* mean, const float* var, float eps,
                            const float* gamma, const float* beta, int act, float slope, int B, int C, int HW, const BnFin& fin,
-                           hipStream_t stream) {
+                           hipStream_t stream, bool cont) {
   if (bn_flat_ok<T>(C, HW, sxb, syb, sxb)) {
     if (bn_v4_ok<T>(HW, x, sxb, y, syb, x, sxb)) {
       const long nvec = (long)B * C * HW / 4;
+      norm_note(cont, "bn_apply_flat_kernel<%s, 4> fin=%d", norm_tn<T>(), fin.ws != nullptr);
       CENET_LAUNCH((bn_apply_flat_kernel<T, 4>), dim3(cdiv(nvec, 256)), dim3(256), stream, x, y, mean, var, eps, gamma, beta, act,
                    slope, C, HW / 4, nvec, fin);
     } else {
       const long nvec = (long)B * C * HW;
+      norm_note(cont, "bn_apply_flat_kernel<%s, 1> fin=%d", norm_tn<T>(), fin.ws != nullptr);
       CENET_LAUNCH((bn_apply_flat_kernel<T, 1>), dim3(cdiv(nvec, 256)), dim3(256), stream, x, y, mean, var, eps, gamma, beta, act,
                    slope, C, HW, nvec, fin);
     }
@@ -1440,11 +1495,13 @@ static int bn_apply_launch(const T* x, long sxb, T* y, long syb, const float* me
   if (bn_v4_ok<T>(HW, x, sxb, y, syb, x, sxb)) {
     int threads, chunks;
     bn_plane_launch(HW / 4, &threads, &chunks);
+    norm_note(cont, "bn_apply_v4_kernel<%s> fin=%d threads=%d chunks=%d", norm_tn<T>(), fin.ws != nullptr, threads, chunks);
     CENET_LAUNCH((bn_apply_v4_kernel<T>), dim3(B * C, chunks), dim3(threads), stream, x, sxb, y, syb, mean, var, eps, gamma,
                  beta, act, slope, C, HW, fin);
   } else {
     int chunks = cdiv(HW, 1024);
     if (chunks > 64) chunks = 64;
+    norm_note(cont, "bn_apply_kernel<%s> fin=%d chunks=%d", norm_tn<T>(), fin.ws != nullptr, chunks);
     CENET_LAUNCH((bn_apply_kernel<T>), dim3(B * C, chunks), dim3(256), stream, x, sxb, y, syb, mean, var, eps, gamma, beta, act,
                  slope, C, HW, fin);
   }
@@ -1455,11 +1512,11 @@ static int bn_apply_launch(const T* x, long sxb, T* y, long syb, const float* me
 template <typename T>
 static int bn_apply_impl(const T* x, long sxb, T* y, long syb, const float* mean, const float* var, float eps,
                          const float* gamma, const float* beta, int act, float slope, int B, int C, int HW,
-                         hipStream_t stream) {
+                         hipStream_t stream, bool cont = false) {
   if (B <= 0 || C <= 0 || HW <= 0) return CENET_EINVAL;
   BnFin fin;
   fin.ws = nullptr; fin.S = 0; fin.n = 0.f; fin.mean = fin.var = fin.rmean = fin.rvar = nullptr; fin.momentum = 0.f; fin.nbt = nullptr; fin.nbt_n = 1;
-  return bn_apply_launch<T>(x, sxb, y, syb, mean, var, eps, gamma, beta, act, slope, B, C, HW, fin, stream);
+  return bn_apply_launch<T>(x, sxb, y, syb, mean, var, eps, gamma, beta, act, slope, B, C, HW, fin, stream, cont);
 }
 
 // train-mode forward: partial sums, then ONE pass that finalises the statistics, normalises, and publishes mean / var /
@@ -1473,12 +1530,13 @@ static int bn_train_fwd_impl(const T* x, long sxb, T* y, long syb, float* ws, fl
     const int rc = bn_stats_impl<T>(x, sxb, B, C, HW, ws, mean, var, running_mean, running_var, momentum, num_batches_tracked,
                                     stream, nbt_count);
     if (rc != CENET_OK) return rc;
-    return bn_apply_impl<T>(x, sxb, y, syb, mean, var, eps, gamma, beta, act, slope, B, C, HW, stream);
+    return bn_apply_impl<T>(x, sxb, y, syb, mean, var, eps, gamma, beta, act, slope, B, C, HW, stream, true);
   }
   if ((long)B * HW <= 256 * BN1K_EPT && (long)B * HW >= 2) {
     BnFin f1;
     f1.ws = nullptr; f1.S = 0; f1.n = (float)((long)B * HW); f1.mean = mean; f1.var = var; f1.rmean = running_mean;
     f1.rvar = running_var; f1.momentum = momentum; f1.nbt = num_batches_tracked; f1.nbt_n = nbt_count;
+    norm_note(false, "bn_train_fwd_1k_kernel");
     CENET_LAUNCH(bn_train_fwd_1k_kernel, dim3(C), dim3(256), stream, (const bf16_t*)x, sxb, (bf16_t*)y, syb, eps, gamma, beta, act,
                  slope, B, HW, f1);
     CENET_CHECK_LAUNCH();
@@ -1488,7 +1546,7 @@ static int bn_train_fwd_impl(const T* x, long sxb, T* y, long syb, float* ws, fl
   fin.S = bn_partial_launch<T>(x, sxb, B, C, HW, ws, stream);
   fin.ws = ws; fin.n = (float)((long)B * HW); fin.mean = mean; fin.var = var; fin.rmean = running_mean; fin.rvar = running_var;
   fin.momentum = momentum; fin.nbt = num_batches_tracked; fin.nbt_n = nbt_count;
-  return bn_apply_launch<T>(x, sxb, y, syb, mean, var, eps, gamma, beta, act, slope, B, C, HW, fin, stream);
+  return bn_apply_launch<T>(x, sxb, y, syb, mean, var, eps, gamma, beta, act, slope, B, C, HW, fin, stream, true);
 }
 CENET_TWIN(bn_train_fwd, (const T* x, long sxb, T* y, long syb, float* ws, float* mean, float* var, float* running_mean,
                           float* running_var, float momentum, long* num_batches_tracked, float eps, const float* gamma,
@@ -1507,6 +1565,7 @@ static int bn_bwd_acc_impl(const T* dy, long sgb, const T* x, long sxb, T* dx, l
   if (B <= 0 || C <= 0 || HW <= 0) return CENET_EINVAL;
   const long total = (long)B * HW;
   if (sizeof(T) == 2 && total <= 256 * BN1K_EPT) {
+    norm_note(false, "bn_bwd_1k_kernel");
     CENET_LAUNCH(bn_bwd_1k_kernel, dim3(C), dim3(256), stream, (const bf16_t*)dy, sgb, (const bf16_t*)x, sxb, (bf16_t*)dx, sdb, mean,
                  var, eps, gamma, beta, act, slope, B, HW, dgamma_acc, dbeta_acc, (const bf16_t*)dx_add, sab);
     CENET_CHECK_LAUNCH();
@@ -1515,6 +1574,8 @@ static int bn_bwd_acc_impl(const T* dy, long sgb, const T* x, long sxb, T* dx, l
   if (bn_flat_ok<T>(C, HW, sgb, sxb, sdb) && (!dx_add || sab == (long)C * HW)) {
     const bool v4 = bn_v4_ok<T>(HW, dy, sgb, x, sxb, dx, sdb) && bn_v4_ok<T>(HW, dx_add, sab, x, sxb, dx, sdb);
     const int S = v4 ? bn_splits_v4(C, total / 4) : bn_splits(C, total);
+    norm_note(false, "%s<%s> S=%d+bn_bwd_apply_flat_kernel<%s, %d>", v4 ? "bn_bwd_partial_v4_kernel" : "bn_bwd_partial_flat_kernel",
+              norm_tn<T>(), S, norm_tn<T>(), v4 ? 4 : 1);
     if (v4)
       CENET_LAUNCH((bn_bwd_partial_v4_kernel<T>), dim3(C, S), dim3(256), stream, dy, sgb, x, sxb, mean, var, eps, gamma, beta, act,
                    slope, B, HW, ws);
@@ -1539,6 +1600,8 @@ static int bn_bwd_acc_impl(const T* dy, long sgb, const T* x, long sxb, T* dx, l
                  slope, B, HW, ws);
     int threads, chunks;
     bn_plane_launch(HW / 4, &threads, &chunks);
+    norm_note(false, "bn_bwd_partial_v4_kernel<%s> S=%d+bn_bwd_apply_v4_kernel<%s> threads=%d chunks=%d", norm_tn<T>(), S, norm_tn<T>(),
+              threads, chunks);
     CENET_LAUNCH((bn_bwd_apply_v4_kernel<T>), dim3(B * C, chunks), dim3(threads), stream, dy, sgb, x, sxb, dx, sdb, mean, var, eps,
                  gamma, beta, act, slope, C, HW, (float)total, (const float*)ws, S, dgamma_acc, dbeta_acc, dx_add, sab);
   } else {
@@ -1547,6 +1610,7 @@ static int bn_bwd_acc_impl(const T* dy, long sgb, const T* x, long sxb, T* dx, l
                  B, HW, ws);
     int chunks = cdiv(HW, 1024);
     if (chunks > 64) chunks = 64;
+    norm_note(false, "bn_bwd_partial_kernel<%s> S=%d+bn_bwd_apply_kernel<%s> chunks=%d", norm_tn<T>(), S, norm_tn<T>(), chunks);
     CENET_LAUNCH((bn_bwd_apply_kernel<T>), dim3(B * C, chunks), dim3(256), stream, dy, sgb, x, sxb, dx, sdb, mean, var, eps, gamma,
                  beta, act, slope, C, HW, (float)total, (const float*)ws, S, dgamma_acc, dbeta_acc, dx_add, sab);
   }

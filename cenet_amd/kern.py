@@ -196,6 +196,14 @@ def last_conv_kernel() -> str:
     return f().decode()
 
 
+def last_norm_kernel() -> str:
+    """what the last call on this thread into norm.hip launched: kernels with template arguments and the run-time numbers that pick a
+    code path, joined by '+' when the call launches several (cenet_norm_last_kernel); test and measurement aid"""
+    f = _lib.lib().cenet_norm_last_kernel
+    f.restype = C.c_char_p
+    return f().decode()
+
+
 # ------------------------------------------------------------------------------------------------
 # generic call helper
 # ------------------------------------------------------------------------------------------------

@@ -268,6 +268,10 @@ int cenet_layernorm_bwd_add_acc_f32(const float* dy, const float* x, const float
  * unet.py:175-197.  ws: CENET_BN_WS_FLOATS(C) floats of scratch (per-split partial sums, no zero-fill needed).
  * stats writes batch mean / biased var and updates the running
  * buffers (momentum, unbiased var) and num_batches_tracked when given. */
+/* Contract of the batch statistics: for ANY data the batch mean is accurate to 2^-24 sqrt(n) E|x| and the biased batch variance to
+ * 2^-24 sqrt(n) (var + (2^-24 sqrt(n) E|x|)^2), n = B HW, times a small constant (tests/norm_ref.py), independent of the value of any
+ * single element: where a kernel sums in one pass, the shift of its sums is a mean over the first min(HW, 64) elements of image 0's
+ * plane, not one element.  ws holds at most 255 partial-sum slots per channel and moment, followed by the C shifts. */
 #define CENET_BN_WS_FLOATS(C) (2L * (C) * 256)
 int cenet_bn_stats_f32(const float* x, long sb, int B, int C, int HW, float* ws, float* mean, float* var,
                        float* running_mean, float* running_var, float momentum, long* num_batches_tracked,
@@ -302,6 +306,11 @@ int cenet_bn1d_train_fwd_f32(const float* z, float* zn, float* mean, float* var,
                              int C, cenet_stream_t stream);
 int cenet_bn1d_bwd_acc_f32(const float* dy, const float* z, float* dz, const float* mean, const float* var, float eps,
                            const float* gamma, float* dgamma_acc, float* dbeta_acc, int B, int C, cenet_stream_t stream);
+
+/* Test and measurement aid: what the last call on this thread into norm.hip launched, kernels with their template arguments and
+ * the run-time numbers that select a code path, joined by '+' where a call launches several ("bn_partial_v4_kernel<float> S=2+
+ * bn_finalize_kernel<float>+bn_apply_v4_kernel<float> fin=0 threads=64 chunks=1").  Written by the host dispatchers only. */
+const char* cenet_norm_last_kernel(void);
 
 /* ---- depthwise 3x3 conv (dwconv.hip) — aten::convolution(groups=C)(+_backward) ------------------------------ */
 /* pvtv2.py:359-370 (token layout), cfam.py:132-140, blocks.py:142-150,305 (NCHW). y = conv(x)+bias; a = act(y) if a. */
