@@ -11,15 +11,10 @@ unpinned; the reference's own printout for the ACDC preset (12.76 G, SURVEY.md s
 from __future__ import annotations
 
 import collections
-import ctypes as C
 
 import torch
 
 from . import _lib
-
-
-def _v(a):
-    return a.value if hasattr(a, "value") else a
 
 
 class _Recorder:
@@ -32,7 +27,6 @@ class _Recorder:
         def fn(*args):
             self._price(name, args)
             return 0
-        fn.restype = None
         return fn
 
     def _price(self, name, a):
@@ -42,27 +36,27 @@ class _Recorder:
                 n = n[:-len(suf)]
         f = 0
         if n == "gemm":
-            M, N, K, nbatch, _, nkb = (_v(x) for x in a[3:9])
+            M, N, K, nbatch, _, nkb = a[3:9]
             f = M * N * K * nbatch * nkb
         elif n == "flash_attn_fwd":
             t = a[0]._obj
             f = t.B * t.H * t.Nq * t.Nk * (t.D + t.Dv)
         elif n == "dwconv3x3_tok":
-            B, Cn, H, W = (_v(x) for x in a[5:9])
+            B, Cn, H, W = a[5:9]
             f = B * Cn * H * W * 9
         elif n == "dwconv3x3_nchw":
-            B, Cn, H, W = (_v(x) for x in a[8:12])
+            B, Cn, H, W = a[8:12]
             f = B * Cn * H * W * 9
         elif n == "layernorm_fwd":
-            f = 5 * _v(a[6]) * _v(a[7])
+            f = 5 * a[6] * a[7]
         elif n == "bn_apply":
-            B, Cn, HW = (_v(x) for x in a[11:14])
+            B, Cn, HW = a[11:14]
             f = B * Cn * HW
         elif n == "bilinear_fwd":
-            B, Cn, _, _, Ho, Wo = (_v(x) for x in a[4:10])
+            B, Cn, _, _, Ho, Wo = a[4:10]
             f = 4 * B * Cn * Ho * Wo
         elif n == "adaptive_avgpool_fwd":
-            B, Cn, Hi, Wi = (_v(x) for x in a[4:8])
+            B, Cn, Hi, Wi = a[4:8]
             f = B * Cn * Hi * Wi
         if f:
             self.flops[n] += int(f)

@@ -15,7 +15,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import EpiT, MatT
+from ._lib import AttnT, DiffAttnT, EpiT, MatT, WgradProbT  # noqa: F401 (the ABI structs, generated from the header)
 
 ACT = {"none": 0, "relu": 1, "lrelu": 2, "gelu": 3, "silu": 4, "sigmoid": 5}
 
@@ -35,7 +35,7 @@ def _chk(*ts):
 
 
 def P(t: Optional[torch.Tensor]):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    return t.data_ptr() if t is not None else None
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -44,10 +44,10 @@ _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 def stream():
     """the current torch stream as a raw hipStream_t (this runs once per kernel launch: keep it cheap)"""
     if _lib.is_hostsim():
-        return C.c_void_p(0)
+        return 0
     if _raw_stream is not None:
-        return C.c_void_p(_raw_stream(torch.cuda.current_device()))
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _raw_stream(torch.cuda.current_device())
+    return torch.cuda.current_stream().cuda_stream
 
 
 # ------------------------------------------------------------------------------------------------
@@ -130,16 +130,8 @@ def gemm(A: MatT, B: MatT, Cout: torch.Tensor, M: int, N: int, K: int, *, scr: i
         e.cKH, e.cKW, e.cPw = col2im["KH"], col2im["KW"], col2im["Pw"]
         e.cHs, e.cWs, e.cstride, e.cpad = col2im["Hs"], col2im["Ws"], col2im["stride"], col2im["pad"]
         e.csci, e.csy, e.csx = col2im["sci"], col2im["sy"], col2im["sx"]
-    fn = _lib.lib().cenet_gemm_bf16 if A.bf16 else _lib.lib().cenet_gemm_f32
-    rc = fn(C.byref(A), C.byref(B), C.byref(e), M, N, K, nbatch, nb_inner, nkb, splits, stream())
-    _lib.check(rc, "cenet_gemm_bf16" if A.bf16 else "cenet_gemm_f32")
-
-
-class WgradProbT(C.Structure):
-    """cenet_wgrad_prob_t (include/cenet_hip.h)."""
-    _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p), ("asum", C.c_void_p),
-                ("lda", C.c_long), ("ldb", C.c_long), ("skbA", C.c_long), ("skbB", C.c_long),
-                ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("nkb", C.c_int), ("akf", C.c_int), ("bkf", C.c_int)]
+    _launch("cenet_gemm_bf16" if A.bf16 else "cenet_gemm_f32", C.byref(A), C.byref(B), C.byref(e), M, N, K, nbatch, nb_inner, nkb,
+            splits)
 
 
 def _wgrad_array(probs):
@@ -157,18 +149,15 @@ def wgrad_group(probs, device, phases=(0,), between=None):
     phases=(1, 2) issues the K-slice launches and the fold launches as two calls (`between()` runs in between): bench.py"""
     n = len(probs)
     arr = _wgrad_array(probs)
-    lib = _lib.lib()
-    f = lib.cenet_wgrad_group_ws_floats
-    f.restype = C.c_long
-    need = int(f(arr, n))
+    need = _lib.lib().cenet_wgrad_group_ws_floats(arr, n)
     ws = torch.empty(max(need, 1), device=device, dtype=torch.float32)
     for i, ph in enumerate(phases):
         if i and between is not None:
             between()
         if ph == 0:
-            _lib.check(lib.cenet_wgrad_group_bf16(arr, n, P(ws), L(need), stream()), "cenet_wgrad_group_bf16")
+            _launch("cenet_wgrad_group_bf16", arr, n, ws, need)
         else:
-            _lib.check(lib.cenet_wgrad_group_phase_bf16(arr, n, P(ws), L(need), int(ph), stream()), "cenet_wgrad_group_phase_bf16")
+            _launch("cenet_wgrad_group_phase_bf16", arr, n, ws, need, ph)
     return need
 
 
@@ -178,30 +167,24 @@ def wgrad_group_plan(probs):
     arr = _wgrad_array(probs)
     out = [(C.c_int * n)() for _ in range(4)]
     _lib.check(_lib.lib().cenet_wgrad_group_plan(arr, n, *out), "cenet_wgrad_group_plan")
-    return [tuple(int(o[i]) for o in out) for i in range(n)]
+    return [tuple(o[i] for o in out) for i in range(n)]
 
 
 def last_gemm_kernel() -> str:
     """name of the kernel instance the last gemm() on this thread launched (as rocprofv3 prints it); measurement aid"""
-    f = _lib.lib().cenet_gemm_last_kernel
-    f.restype = C.c_char_p
-    return f().decode()
+    return _lib.lib().cenet_gemm_last_kernel().decode()
 
 
 def last_conv_kernel() -> str:
     """what the last call on this thread into conv_direct.hip / conv_c1.hip / dwconv.hip launched: the kernel with its template
     arguments and the run-time numbers that pick a code path inside it (cenet_conv_last_kernel); test and measurement aid"""
-    f = _lib.lib().cenet_conv_last_kernel
-    f.restype = C.c_char_p
-    return f().decode()
+    return _lib.lib().cenet_conv_last_kernel().decode()
 
 
 def last_norm_kernel() -> str:
     """what the last call on this thread into norm.hip launched: kernels with template arguments and the run-time numbers that pick a
     code path, joined by '+' when the call launches several (cenet_norm_last_kernel); test and measurement aid"""
-    f = _lib.lib().cenet_norm_last_kernel
-    f.restype = C.c_char_p
-    return f().decode()
+    return _lib.lib().cenet_norm_last_kernel().decode()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -218,49 +201,31 @@ class Ptr:
         return self.t.data_ptr() + esz(self.t) * self.off
 
 
+def _launch(name, *args):
+    """call entry point `name` on the current stream: tensors and `Ptr` go as their data pointer (None: NULL), everything else
+    as it is — include/cenet_hip.h types it (_lib.bind)"""
+    args = [a.data_ptr() if isinstance(a, (torch.Tensor, Ptr)) else a for a in args]
+    _lib.check(getattr(_lib.lib(), name)(*args, stream()), name)
+
+
 def _call(name, *args):
-    """name ends in `_f32`; a bf16 tensor among the arguments selects the `_bf16` twin (all activation arguments of one call
-    share their element type)"""
+    """_launch where `name` ends in `_f32` and a bf16 tensor among the arguments selects the `_bf16` twin (all activation
+    arguments of one call share their element type); one pass over the arguments, this is the hot path of an eager step"""
     cargs = []
     bf = False
     for a in args:
         if isinstance(a, (torch.Tensor, Ptr)):
             bf = bf or a.dtype == BF16
-            cargs.append(C.c_void_p(a.data_ptr()))
-        elif a is None:
-            cargs.append(C.c_void_p(0))
-        elif isinstance(a, float):
-            cargs.append(C.c_float(a))
-        elif isinstance(a, bool):
-            cargs.append(C.c_int(int(a)))
-        elif isinstance(a, int):
-            cargs.append(C.c_long(a) if abs(a) > 0x7FFFFFFF else C.c_int(a))
-        else:
-            cargs.append(a)
+            a = a.data_ptr()
+        cargs.append(a)
     if bf and not name.endswith("_bf16"):  # (entries that exist for bf16 tensors only are named so by the caller)
         assert name.endswith("_f32"), name
         name = name[:-4] + "_bf16"
-    rc = getattr(_lib.lib(), name)(*cargs, stream())
-    _lib.check(rc, name)
-
-
-def L(v: int):
-    """force a C long argument"""
-    return C.c_long(int(v))
-
-
-class AttnT(C.Structure):
-    """cenet_attn_t (include/cenet_hip.h)."""
-    _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("o", C.c_void_p), ("lse", C.c_void_p),
-                ("dout", C.c_void_p), ("dq", C.c_void_p), ("dk", C.c_void_p), ("dv", C.c_void_p), ("delta", C.c_void_p)] + \
-               [(n, C.c_long) for n in ("qsb", "qsh", "qsi", "qsd", "ksb", "ksh", "ksi", "ksd", "vsb", "vsh", "vsi", "vsd",
-                                        "osb", "osh", "osi", "osd")] + \
-               [(n, C.c_int) for n in ("B", "H", "Nq", "Nk", "D", "Dv", "v_head_div")] + [("scale", C.c_float)] + \
-               [("dkv_zeroed", C.c_int), ("dkv_f32", C.c_int), ("finite_scores", C.c_int)]
+    _lib.check(getattr(_lib.lib(), name)(*cargs, stream()), name)
 
 
 def flash_supported(D: int, Dv: int) -> bool:
-    return bool(_lib.lib().cenet_flash_attn_supported(int(D), int(Dv)))
+    return bool(_lib.lib().cenet_flash_attn_supported(D, Dv))
 
 
 def flashb_supported(D: int, Dv: int) -> bool:
@@ -270,111 +235,96 @@ def flashb_supported(D: int, Dv: int) -> bool:
 
 def flash_fwd(a: AttnT, bf16: bool = False):
     name = "cenet_flash_attn_fwd_bf16" if bf16 else "cenet_flash_attn_fwd_f32"
-    _lib.check(getattr(_lib.lib(), name)(C.byref(a), stream()), name)
+    _launch(name, C.byref(a))
 
 
 def flash_bwd(a: AttnT, bf16: bool = False):
     name = "cenet_flash_attn_bwd_bf16" if bf16 else "cenet_flash_attn_bwd_f32"
-    _lib.check(getattr(_lib.lib(), name)(C.byref(a), stream()), name)
-
-
-class DiffAttnT(C.Structure):
-    """cenet_diffattn_t (include/cenet_hip.h)."""
-    _fields_ = [(n, C.c_void_p) for n in ("q", "k", "v", "U", "lse", "dU", "dq", "dk", "dv", "ws")] + \
-               [(n, C.c_int) for n in ("B", "H", "N", "hd")] + [("scale", C.c_float), ("batch_mul", C.c_int)]
+    _launch(name, C.byref(a))
 
 
 def diffattn_heads_supported(hd: int, N: int) -> bool:
-    return bool(_lib.lib().cenet_diffattn_heads_supported(int(hd), int(N)))
+    return bool(_lib.lib().cenet_diffattn_heads_supported(hd, N))
 
 
 def diffattn_heads_ws_bytes(B: int, H: int, N: int) -> int:
-    fn = _lib.lib().cenet_diffattn_heads_ws_bytes
-    fn.restype = C.c_long
-    return int(fn(int(B), int(H), int(N)))
+    return _lib.lib().cenet_diffattn_heads_ws_bytes(B, H, N)
 
 
 def diffattn_heads(a: DiffAttnT, backward: bool):
     name = "cenet_diffattn_heads_bwd_bf16" if backward else "cenet_diffattn_heads_fwd_bf16"
-    _lib.check(getattr(_lib.lib(), name)(C.byref(a), stream()), name)
+    _launch(name, C.byref(a))
 
 
 def attn64_ws_bytes(B: int, H: int, N: int) -> int:
-    fn = _lib.lib().cenet_attn64_ws_bytes
-    fn.restype = C.c_long
-    return int(fn(int(B), int(H), int(N)))
+    return _lib.lib().cenet_attn64_ws_bytes(B, H, N)
 
 
 def attn64(a: DiffAttnT, backward: bool):
     """plain self-attention, head dimension 64, bf16 token-major tensors (attn_diff.hip, single-softmax form)"""
     name = "cenet_attn64_bwd_bf16" if backward else "cenet_attn64_fwd_bf16"
-    _lib.check(getattr(_lib.lib(), name)(C.byref(a), stream()), name)
+    _launch(name, C.byref(a))
 
 
 def sra_attn_bwd_supported(hd: int, Nk: int) -> bool:
-    return bool(_lib.lib().cenet_sra_attn_bwd_supported(int(hd), int(Nk)))
+    return bool(_lib.lib().cenet_sra_attn_bwd_supported(hd, Nk))
 
 
 def sra_attn_bwd_blocks_supported(hd: int, Nk: int) -> bool:
-    return bool(_lib.lib().cenet_sra_attn_bwd_blocks_supported(int(hd), int(Nk)))
+    return bool(_lib.lib().cenet_sra_attn_bwd_blocks_supported(hd, Nk))
 
 
 def sra_attn_fwd(q, kv, o, lse, B, H, Nq, Nk, scale):
     """spatial-reduction attention forward with resident keys (bf16, head dim 64, <= 64 keys): o and the natural-log lse"""
     _chk(q, kv, o, lse)
     assert q.dtype == BF16 and kv.dtype == BF16 and o.dtype == BF16 and lse.dtype == torch.float32
-    rc = _lib.lib().cenet_sra_attn_fwd_bf16(P(q), P(kv), P(o), P(lse), B, H, Nq, Nk, C.c_float(scale), stream())
-    _lib.check(rc, "cenet_sra_attn_fwd_bf16")
+    _launch("cenet_sra_attn_fwd_bf16", q, kv, o, lse, B, H, Nq, Nk, scale)
 
 
 def sra_attn_bwd(q, kv, o, dout, lse, dq, dkv, B, H, Nq, Nk, scale):
     """fused spatial-reduction attention backward (bf16, head dim 64, <= 64 keys); dkv: fp32, zero-filled"""
     _chk(q, kv, o, dout, lse, dq, dkv)
     assert q.dtype == BF16 and kv.dtype == BF16 and dq.dtype == BF16 and dkv.dtype == torch.float32
-    rc = _lib.lib().cenet_sra_attn_bwd_bf16(P(q), P(kv), P(o), P(dout), P(lse), P(dq), P(dkv), B, H, Nq, Nk, C.c_float(scale),
-                                            stream())
-    _lib.check(rc, "cenet_sra_attn_bwd_bf16")
+    _launch("cenet_sra_attn_bwd_bf16", q, kv, o, dout, lse, dq, dkv, B, H, Nq, Nk, scale)
 
 
 def sra_attn_bwd_direct_supported(B, H, Nq, Nk) -> bool:
-    return bool(_lib.lib().cenet_sra_attn_bwd_direct_supported(int(B), int(H), int(Nq), int(Nk)))
+    return bool(_lib.lib().cenet_sra_attn_bwd_direct_supported(B, H, Nq, Nk))
 
 
 def sra_attn_bwd_direct(q, kv, o, dout, lse, dq, dkv, B, H, Nq, Nk, scale):
     """as sra_attn_bwd where one workgroup owns a (batch, head): dkv bf16, written (not accumulated)"""
     _chk(q, kv, o, dout, lse, dq, dkv)
     assert q.dtype == BF16 and kv.dtype == BF16 and dq.dtype == BF16 and dkv.dtype == BF16
-    rc = _lib.lib().cenet_sra_attn_bwd_direct_bf16(P(q), P(kv), P(o), P(dout), P(lse), P(dq), P(dkv), B, H, Nq, Nk,
-                                                   C.c_float(scale), stream())
-    _lib.check(rc, "cenet_sra_attn_bwd_direct_bf16")
+    _launch("cenet_sra_attn_bwd_direct_bf16", q, kv, o, dout, lse, dq, dkv, B, H, Nq, Nk, scale)
 
 
 def softmax_rows_fwd(x, y, rows, n):
     _chk(x, y)
-    _call("cenet_softmax_rows_fwd_f32", x, y, L(rows), n)
+    _call("cenet_softmax_rows_fwd_f32", x, y, rows, n)
 
 
 def softmax_rows_bwd(y, dy, dx, rows, n):
     _chk(y, dy, dx)
-    _call("cenet_softmax_rows_bwd_f32", y, dy, dx, L(rows), n)
+    _call("cenet_softmax_rows_bwd_f32", y, dy, dx, rows, n)
 
 
 def softmax_rows_finite_fwd(x, y, rows, n):
     """fp32 parity mode: the scores x pass through torch.nan_to_num before the softmax (multihead_diffattn.py:106)"""
     _chk(x, y)
-    _call("cenet_softmax_rows_finite_fwd_f32", x, y, L(rows), n)
+    _call("cenet_softmax_rows_finite_fwd_f32", x, y, rows, n)
 
 
 def softmax_rows_finite_bwd(y, dy, x, dx, rows, n):
     """... and dx = 0 where the raw score x was not finite (nan_to_num's backward)"""
     _chk(y, dy, x, dx)
-    _call("cenet_softmax_rows_finite_bwd_f32", y, dy, x, dx, L(rows), n)
+    _call("cenet_softmax_rows_finite_bwd_f32", y, dy, x, dx, rows, n)
 
 
 # ---- norms -----------------------------------------------------------------------------------------
 def layernorm_fwd(x, gamma, beta, y, mean, rstd, rows, Cn, eps):
     _chk(x, gamma, beta, y, mean, rstd)
-    _call("cenet_layernorm_fwd_f32", x, gamma, beta, y, mean, rstd, rows, Cn, float(eps))
+    _call("cenet_layernorm_fwd_f32", x, gamma, beta, y, mean, rstd, rows, Cn, eps)
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, Cn, dx_add=None):
@@ -391,7 +341,7 @@ def layernorm_bwd_part(dy, x, gamma, mean, rstd, dx, rows, Cn, dx_add=None, bsca
     ln_fold_group adds the column sums of many such buffers into their gradients with one launch.
     bscale [B] + dxs (like dx): also write dxs = bscale[sample] * dx (what scale_batch(dx, bscale) would)."""
     _chk(dy, x, gamma, mean, rstd, dx, dx_add, bscale, dxs)
-    nrows = int(_lib.lib().cenet_layernorm_bwd_part_rows(rows, Cn))
+    nrows = _lib.lib().cenet_layernorm_bwd_part_rows(rows, Cn)
     part = torch.empty((nrows, 2 * Cn), device=dy.device, dtype=torch.float32)
     if bscale is None:
         _call("cenet_layernorm_bwd_add_part_bf16", dy, x, gamma, mean, rstd, dx_add, dx, part, rows, Cn)
@@ -411,45 +361,41 @@ def ln_fold_group(items):
     dbs = (C.c_void_p * n)(*[t[2].data_ptr() for t in items])
     nr = (C.c_int * n)(*[t[0].shape[0] for t in items])
     cs = (C.c_int * n)(*[t[0].shape[1] // 2 for t in items])
-    rc = _lib.lib().cenet_ln_fold_group(parts, dgs, dbs, nr, cs, n, stream())
-    _lib.check(rc, "cenet_ln_fold_group")
+    _launch("cenet_ln_fold_group", parts, dgs, dbs, nr, cs, n)
 
 
 def bn_stats(x, sb, B, Cn, HW, ws, mean, var, rmean, rvar, momentum, nbt):
     _chk(x, ws, mean, var, rmean, rvar)
-    _call("cenet_bn_stats_f32", x, L(sb), B, Cn, HW, ws, mean, var, rmean, rvar, float(momentum), nbt)
+    _call("cenet_bn_stats_f32", x, sb, B, Cn, HW, ws, mean, var, rmean, rvar, momentum, nbt)
 
 
 def bn1d_supported(B: int) -> bool:
-    return bool(_lib.lib().cenet_bn1d_supported(int(B)))
+    return bool(_lib.lib().cenet_bn1d_supported(B))
 
 
 def bn1d_train_fwd(z, zn, mean, var, rmean, rvar, momentum, nbt, eps, gamma, beta, B, Cn):
     """train-mode BatchNorm1d of a [B, C] fp32 matrix (2 <= B <= 64) in one launch: zn, mean / var, running statistics, counter"""
     _chk(z, zn, mean, var, rmean, rvar, gamma, beta)
     assert z.dtype == torch.float32 and zn.dtype == torch.float32
-    _lib.check(_lib.lib().cenet_bn1d_train_fwd_f32(P(z), P(zn), P(mean), P(var), P(rmean), P(rvar), C.c_float(momentum), P(nbt),
-                                                   C.c_float(eps), P(gamma), P(beta), int(B), int(Cn), stream()),
-               "cenet_bn1d_train_fwd_f32")
+    _launch("cenet_bn1d_train_fwd_f32", z, zn, mean, var, rmean, rvar, momentum, nbt, eps, gamma, beta, B, Cn)
 
 
 def bn1d_bwd(dy, z, dz, mean, var, eps, gamma, dgamma, dbeta, B, Cn):
     _chk(dy, z, dz, mean, var, gamma, dgamma, dbeta)
     assert dy.dtype == torch.float32 and z.dtype == torch.float32
-    _lib.check(_lib.lib().cenet_bn1d_bwd_acc_f32(P(dy), P(z), P(dz), P(mean), P(var), C.c_float(eps), P(gamma), P(dgamma), P(dbeta),
-                                                 int(B), int(Cn), stream()), "cenet_bn1d_bwd_acc_f32")
+    _launch("cenet_bn1d_bwd_acc_f32", dy, z, dz, mean, var, eps, gamma, dgamma, dbeta, B, Cn)
 
 
 def bn_train_fwd(x, sxb, y, syb, ws, mean, var, rmean, rvar, momentum, nbt, eps, gamma, beta, act, slope, B, Cn, HW):
     """train-mode BatchNorm forward: statistics + normalisation (+ activation), mean / var / running statistics written"""
     _chk(x, y, ws, mean, var, rmean, rvar, gamma, beta)
-    _call("cenet_bn_train_fwd_f32", x, L(sxb), y, L(syb), ws, mean, var, rmean, rvar, float(momentum), nbt, float(eps), gamma,
-          beta, ACT[act], float(slope), B, Cn, HW, int(nbt.numel()) if nbt is not None else 1)
+    _call("cenet_bn_train_fwd_f32", x, sxb, y, syb, ws, mean, var, rmean, rvar, momentum, nbt, eps, gamma,
+          beta, ACT[act], slope, B, Cn, HW, nbt.numel() if nbt is not None else 1)
 
 
 def bn_apply(x, sxb, y, syb, mean, var, eps, gamma, beta, act, slope, B, Cn, HW):
     _chk(x, y, mean, var, gamma, beta)
-    _call("cenet_bn_apply_f32", x, L(sxb), y, L(syb), mean, var, float(eps), gamma, beta, ACT[act], float(slope), B, Cn, HW)
+    _call("cenet_bn_apply_f32", x, sxb, y, syb, mean, var, eps, gamma, beta, ACT[act], slope, B, Cn, HW)
 
 
 def bn_bwd(dy, sgb, x, sxb, dx, sdb, mean, var, eps, gamma, beta, act, slope, B, Cn, HW, ws, dgamma, dbeta, dx_add=None):
@@ -457,50 +403,46 @@ def bn_bwd(dy, sgb, x, sxb, dx, sdb, mean, var, eps, gamma, beta, act, slope, B,
     around the BatchNorm)"""
     _chk(dy, x, dx, mean, var, gamma, beta, ws, dgamma, dbeta, dx_add)
     if dx_add is None:
-        _call("cenet_bn_bwd_acc_f32", dy, L(sgb), x, L(sxb), dx, L(sdb), mean, var, float(eps), gamma, beta, ACT[act],
-              float(slope), B, Cn, HW, ws, dgamma, dbeta)
+        _call("cenet_bn_bwd_acc_f32", dy, sgb, x, sxb, dx, sdb, mean, var, eps, gamma, beta, ACT[act],
+              slope, B, Cn, HW, ws, dgamma, dbeta)
     else:
-        _call("cenet_bn_bwd_add_acc_f32", dy, L(sgb), x, L(sxb), dx, L(sdb), dx_add, L(Cn * HW), mean, var, float(eps), gamma, beta,
-              ACT[act], float(slope), B, Cn, HW, ws, dgamma, dbeta)
+        _call("cenet_bn_bwd_add_acc_f32", dy, sgb, x, sxb, dx, sdb, dx_add, Cn * HW, mean, var, eps, gamma, beta,
+              ACT[act], slope, B, Cn, HW, ws, dgamma, dbeta)
 
 
 def res_tail_supported(x2, x3) -> bool:
     return bool(is_bf16(x2) and is_bf16(x3) and x2.dim() == 4 and x2.shape == x3.shape and x2.data_ptr() % 16 == 0
-                and x3.data_ptr() % 16 == 0 and _lib.lib().cenet_res_tail_supported(int(x2.shape[2]), int(x2.shape[3])))
+                and x3.data_ptr() % 16 == 0 and _lib.lib().cenet_res_tail_supported(x2.shape[2], x2.shape[3]))
 
 
 def res_tail_fwd(x2, x3, mean2, var2, g2, b2, eps2, mean3, var3, g3, b3, eps3, w, slope, out, B, Cn, H, W):
     """out = w[c] * MaxPool2x2(LeakyReLU(BN2(x2) + BN3(x3))) from the batch statistics, one launch (csrc/res_tail.hip)"""
     _chk(x2, x3, mean2, var2, g2, b2, mean3, var3, g3, b3, w, out)
-    _call("cenet_res_tail_fwd_bf16", x2, x3, mean2, var2, g2, b2, float(eps2), mean3, var3, g3, b3, float(eps3), w, float(slope), out,
+    _call("cenet_res_tail_fwd_bf16", x2, x3, mean2, var2, g2, b2, eps2, mean3, var3, g3, b3, eps3, w, slope, out,
           B, Cn, H, W)
 
 
 def res_tail_bwd(g, x2, x3, mean2, var2, g2, b2, eps2, mean3, var3, g3, b3, eps3, w, slope, dx2, dx3, dg2, db2, dg3, db3, dw, B, Cn,
                  H, W):
     _chk(g, x2, x3, mean2, var2, g2, b2, mean3, var3, g3, b3, w, dx2, dx3, dg2, db2, dg3, db3, dw)
-    f = _lib.lib().cenet_res_tail_bwd_ws_floats
-    f.restype = C.c_long
-    ws = torch.empty(int(f(Cn)), device=g.device, dtype=torch.float32)
-    _call("cenet_res_tail_bwd_bf16", g, x2, x3, mean2, var2, g2, b2, float(eps2), mean3, var3, g3, b3, float(eps3), w, float(slope),
+    ws = torch.empty(_lib.lib().cenet_res_tail_bwd_ws_floats(Cn), device=g.device, dtype=torch.float32)
+    _call("cenet_res_tail_bwd_bf16", g, x2, x3, mean2, var2, g2, b2, eps2, mean3, var3, g3, b3, eps3, w, slope,
           dx2, dx3, dg2, db2, dg3, db3, dw, ws, B, Cn, H, W)
 
 
 def res_tail_img_fwd(x2, img, mean2, var2, g2, b2, eps2, imean, ivar, w3, g3, b3, eps3, rm3, rv3, nbt3, mom3, w, slope, out, B, Cn, H, W):
     """res_tail_fwd with the shortcut x3 = w3[c] * img not materialised (one-channel input); updates BatchNorm3's running statistics"""
     _chk(x2, img, mean2, var2, g2, b2, imean, ivar, w3, g3, b3, rm3, rv3, w, out)
-    _call("cenet_res_tail_img_fwd_bf16", x2, img, mean2, var2, g2, b2, float(eps2), imean, ivar, w3, g3, b3, float(eps3), rm3, rv3, nbt3,
-          float(mom3), w, float(slope), out, B, Cn, H, W)
+    _call("cenet_res_tail_img_fwd_bf16", x2, img, mean2, var2, g2, b2, eps2, imean, ivar, w3, g3, b3, eps3, rm3, rv3, nbt3,
+          mom3, w, slope, out, B, Cn, H, W)
 
 
 def res_tail_img_bwd(g, x2, img, mean2, var2, g2, b2, eps2, imean, ivar, w3, g3, b3, eps3, w, slope, dx2, dg2, db2, dg3, db3, dw3, dw,
                      B, Cn, H, W):
     _chk(g, x2, img, mean2, var2, g2, b2, imean, ivar, w3, g3, b3, w, dx2, dg2, db2, dg3, db3, dw3, dw)
-    f = _lib.lib().cenet_res_tail_bwd_ws_floats
-    f.restype = C.c_long
-    ws = torch.empty(int(f(Cn)), device=g.device, dtype=torch.float32)
-    _call("cenet_res_tail_img_bwd_bf16", g, x2, img, mean2, var2, g2, b2, float(eps2), imean, ivar, w3, g3, b3, float(eps3), w,
-          float(slope), dx2, dg2, db2, dg3, db3, dw3, dw, ws, B, Cn, H, W)
+    ws = torch.empty(_lib.lib().cenet_res_tail_bwd_ws_floats(Cn), device=g.device, dtype=torch.float32)
+    _call("cenet_res_tail_img_bwd_bf16", g, x2, img, mean2, var2, g2, b2, eps2, imean, ivar, w3, g3, b3, eps3, w,
+          slope, dx2, dg2, db2, dg3, db3, dw3, dw, ws, B, Cn, H, W)
 
 
 # ---- depthwise conv ------------------------------------------------------------------------------------
@@ -510,66 +452,66 @@ _NO_CHANLOC = __import__("os").environ.get("CENET_NO_CHANLOC") is not None  # me
 
 def eucb_supported(x) -> bool:
     B, _, H, W = x.shape
-    return (not _NO_CHANLOC) and bool(_lib.lib().cenet_eucb_supported(int(B), int(H), int(W), esz(x)))
+    return (not _NO_CHANLOC) and bool(_lib.lib().cenet_eucb_supported(B, H, W, esz(x)))
 
 
 def eucb_fwd(x, w, gamma, beta, eps, slope, y, mean, var, rmean, rvar, momentum, nbt, B, Cn, H, W):
     _chk(x, w, gamma, beta, y, mean, var, rmean, rvar)
-    _call("cenet_eucb_fwd_f32", x, L(Cn * H * W), w, gamma, beta, float(eps), float(slope), y, L(4 * Cn * H * W), mean, var, rmean,
-          rvar, float(momentum), nbt, B, Cn, H, W)
+    _call("cenet_eucb_fwd_f32", x, Cn * H * W, w, gamma, beta, eps, slope, y, 4 * Cn * H * W, mean, var, rmean,
+          rvar, momentum, nbt, B, Cn, H, W)
 
 
 def eucb_bwd(g, x, w, gamma, beta, eps, slope, mean, var, dx, dw, dgamma, dbeta, B, Cn, H, W):
     _chk(g, x, w, gamma, beta, mean, var, dx, dw, dgamma, dbeta)
-    _call("cenet_eucb_bwd_acc_f32", g, L(4 * Cn * H * W), x, L(Cn * H * W), w, gamma, beta, float(eps), float(slope), mean, var, dx,
-          L(Cn * H * W), dw, dgamma, dbeta, B, Cn, H, W)
+    _call("cenet_eucb_bwd_acc_f32", g, 4 * Cn * H * W, x, Cn * H * W, w, gamma, beta, eps, slope, mean, var, dx,
+          Cn * H * W, dw, dgamma, dbeta, B, Cn, H, W)
 
 
 def chanloc_supported(B: int, HW: int) -> bool:
-    return (not _NO_CHANLOC) and bool(_lib.lib().cenet_chanloc_supported(int(B), int(HW)))
+    return (not _NO_CHANLOC) and bool(_lib.lib().cenet_chanloc_supported(B, HW))
 
 
 def cfam_mid_fwd(p_raw, m, x0, x1, y2, gp, bp, epsp, meanp, varp, rmp, rvp, momp, nbtp, w, ls, g2, b2, eps2, mean2, var2, rm2, rv2,
                  mom2, nbt2, B, Cn, HW):
     _chk(p_raw, m, x0, x1, y2, gp, bp, meanp, varp, w, ls, g2, b2, mean2, var2)
-    _call("cenet_cfam_mid_fwd_f32", p_raw, m, x0, x1, y2, gp, bp, float(epsp), meanp, varp, rmp, rvp, float(momp), nbtp, w, ls, g2,
-          b2, float(eps2), mean2, var2, rm2, rv2, float(mom2), nbt2, B, Cn, HW)
+    _call("cenet_cfam_mid_fwd_f32", p_raw, m, x0, x1, y2, gp, bp, epsp, meanp, varp, rmp, rvp, momp, nbtp, w, ls, g2,
+          b2, eps2, mean2, var2, rm2, rv2, mom2, nbt2, B, Cn, HW)
 
 
 def cfam_mid_bwd(g_y2, g_x1, p_raw, m, x1, d_p, d_m, d_x0, gp, bp, epsp, meanp, varp, w, ls, g2, eps2, mean2, var2, dgp, dbp, dw, dls,
                  dg2, db2, B, Cn, HW):
     _chk(g_y2, g_x1, p_raw, m, x1, d_p, d_m, d_x0)
-    _call("cenet_cfam_mid_bwd_acc_f32", g_y2, g_x1, p_raw, m, x1, d_p, d_m, d_x0, gp, bp, float(epsp), meanp, varp, w, ls, g2,
-          float(eps2), mean2, var2, dgp, dbp, dw, dls, dg2, db2, B, Cn, HW)
+    _call("cenet_cfam_mid_bwd_acc_f32", g_y2, g_x1, p_raw, m, x1, d_p, d_m, d_x0, gp, bp, epsp, meanp, varp, w, ls, g2,
+          eps2, mean2, var2, dgp, dbp, dw, dls, dg2, db2, B, Cn, HW)
 
 
 def dwbn_fwd(x, ws, dils, g, p, v, rest, gamma, beta, eps, mean, var, rmean, rvar, momentum, nbt, B, H, W):
     """MultiOrderDWConv's dilated depthwise branches + BatchNorm + ReLU and the pooled slice's copy in one launch (chanloc.hip)"""
     _chk(x, v, rest, gamma, beta, mean, var, rmean, rvar, *ws)
     nb, Ct = len(ws), len(ws) * g + p
-    _call("cenet_dwbn_fwd_f32", x, L(Ct * H * W), _ptr_arr([w.data_ptr() for w in ws]), (C.c_int * nb)(*[int(d) for d in dils]), nb,
-          g, p, v, L(nb * g * H * W), rest, L(p * H * W), gamma, beta, float(eps), mean, var, rmean, rvar, float(momentum), nbt, B, H, W)
+    _call("cenet_dwbn_fwd_f32", x, Ct * H * W, _ptr_arr([w.data_ptr() for w in ws]), (C.c_int * nb)(*dils), nb,
+          g, p, v, nb * g * H * W, rest, p * H * W, gamma, beta, eps, mean, var, rmean, rvar, momentum, nbt, B, H, W)
 
 
 def dwbn_bwd(g_v, g_rest, x, ws, dils, g, p, gamma, beta, eps, mean, var, dx, dws, dgamma, dbeta, B, H, W):
     _chk(g_v, g_rest, x, dx, dgamma, dbeta, *ws, *dws)
     nb, Ct = len(ws), len(ws) * g + p
-    _call("cenet_dwbn_bwd_acc_f32", g_v, L(nb * g * H * W), g_rest, L(p * H * W), None, L(0), x, L(Ct * H * W),
-          _ptr_arr([w.data_ptr() for w in ws]), (C.c_int * nb)(*[int(d) for d in dils]), nb, g, p, gamma, beta, float(eps), mean, var,
-          dx, L(Ct * H * W), _ptr_arr([w.data_ptr() for w in dws]), dgamma, dbeta, B, H, W)
+    _call("cenet_dwbn_bwd_acc_f32", g_v, nb * g * H * W, g_rest, p * H * W, None, 0, x, Ct * H * W,
+          _ptr_arr([w.data_ptr() for w in ws]), (C.c_int * nb)(*dils), nb, g, p, gamma, beta, eps, mean, var,
+          dx, Ct * H * W, _ptr_arr([w.data_ptr() for w in dws]), dgamma, dbeta, B, H, W)
 
 
 def cfam_front_fwd(x0, y1, xs, g1, b1, eps1, mean1, var1, rm1, rv1, mom1, nbt1, fc1, fc2, gd, bd, epsd, meand, vard, rmd, rvd, momd,
                    nbtd, u, amax, z, zn, B, Cn, HW):
     _chk(x0, y1, xs, g1, b1, mean1, var1, fc1, fc2, u, amax, z, zn)
-    _call("cenet_cfam_front_fwd_f32", x0, y1, xs, g1, b1, float(eps1), mean1, var1, rm1, rv1, float(mom1), nbt1, fc1, fc2, gd, bd,
-          float(epsd), meand, vard, rmd, rvd, float(momd), nbtd, u, amax, z, zn, B, Cn, HW)
+    _call("cenet_cfam_front_fwd_f32", x0, y1, xs, g1, b1, eps1, mean1, var1, rm1, rv1, mom1, nbt1, fc1, fc2, gd, bd,
+          epsd, meand, vard, rmd, rvd, momd, nbtd, u, amax, z, zn, B, Cn, HW)
 
 
 def cfam_front_bwd(g_xs, g_y1, g_tap, x0, dx0, g1, b1, eps1, mean1, var1, fc1, fc2, gd, epsd, meand, vard, u, amax, z, zn, dg1, db1,
                    dfc1, dfc2, dgd, dbd, B, Cn, HW):
     _chk(g_xs, g_y1, g_tap, x0, dx0)
-    _call("cenet_cfam_front_bwd_acc_f32", g_xs, g_y1, g_tap, x0, dx0, g1, b1, float(eps1), mean1, var1, fc1, fc2, gd, float(epsd),
+    _call("cenet_cfam_front_bwd_acc_f32", g_xs, g_y1, g_tap, x0, dx0, g1, b1, eps1, mean1, var1, fc1, fc2, gd, epsd,
           meand, vard, u, amax, z, zn, dg1, db1, dfc1, dfc2, dgd, dbd, B, Cn, HW)
 
 
@@ -580,12 +522,12 @@ def dwact_supported(x) -> bool:
 
 def dwact_fwd(x, w, bias, y, act, slope, dil, B, Cn, H, W):
     _chk(x, w, bias, y)
-    _call("cenet_dwact_fwd_f32", x, w, bias, y, ACT[act], float(slope), dil, B, Cn, H, W)
+    _call("cenet_dwact_fwd_f32", x, w, bias, y, ACT[act], slope, dil, B, Cn, H, W)
 
 
 def dwact_bwd(g, x, w, bias, dx, dw, db, act, slope, dil, B, Cn, H, W):
     _chk(g, x, w, bias, dx, dw, db)
-    _call("cenet_dwact_bwd_acc_f32", g, x, w, bias, dx, dw, db, ACT[act], float(slope), dil, B, Cn, H, W)
+    _call("cenet_dwact_bwd_acc_f32", g, x, w, bias, dx, dw, db, ACT[act], slope, dil, B, Cn, H, W)
 
 
 def pool_branch_supported(B, P, H, W) -> bool:
@@ -594,21 +536,21 @@ def pool_branch_supported(B, P, H, W) -> bool:
 
 def pool_branch_fwd(x, sxb, wc, gamma, beta, eps, slope, RH, RW, y, syb, pooled, t, mean, var, rmean, rvar, momentum, nbt, B, P, H, W):
     _chk(x, wc, gamma, beta, RH, RW, y, pooled, t, mean, var, rmean, rvar)
-    _call("cenet_pool_branch_fwd_f32", x, L(sxb), wc, gamma, beta, float(eps), float(slope), RH, RW, y, L(syb), pooled, t, mean, var,
-          rmean, rvar, float(momentum), nbt, B, P, H, W)
+    _call("cenet_pool_branch_fwd_f32", x, sxb, wc, gamma, beta, eps, slope, RH, RW, y, syb, pooled, t, mean, var,
+          rmean, rvar, momentum, nbt, B, P, H, W)
 
 
 def pool_branch_bwd(g, sgb, wc, gamma, beta, eps, slope, RH, RW, pooled, t, mean, var, dt_ws, dx, sdb, dwc, dgamma, dbeta, B, P, H, W):
     _chk(g, wc, gamma, beta, RH, RW, pooled, t, mean, var, dt_ws, dx, dwc, dgamma, dbeta)
-    _call("cenet_pool_branch_bwd_acc_f32", g, L(sgb), wc, gamma, beta, float(eps), float(slope), RH, RW, pooled, t, mean, var, dt_ws,
-          dx, L(sdb), dwc, dgamma, dbeta, B, P, H, W)
+    _call("cenet_pool_branch_bwd_acc_f32", g, sgb, wc, gamma, beta, eps, slope, RH, RW, pooled, t, mean, var, dt_ws,
+          dx, sdb, dwc, dgamma, dbeta, B, P, H, W)
 
 
 def dw_nchw(x, sxb, w, bias, y, syb, a, sab, B, Cn, H, W, dil, flip, act="none", slope=0.0, x_off=0, y_off=0):
     """x_off / y_off (elements): read / write a channel slice of a wider tensor in place (batch strides sxb / syb)"""
     _chk(x, w, bias, y, a)
-    _call("cenet_dwconv3x3_nchw_f32", Ptr(x, x_off), L(sxb), w, bias, Ptr(y, y_off) if y is not None else None, L(syb), a, L(sab),
-          B, Cn, H, W, dil, int(flip), ACT[act], float(slope))
+    _call("cenet_dwconv3x3_nchw_f32", Ptr(x, x_off), sxb, w, bias, Ptr(y, y_off) if y is not None else None, syb, a, sab,
+          B, Cn, H, W, dil, flip, ACT[act], slope)
 
 
 
@@ -634,7 +576,7 @@ def dw_nchw_multi(branches, B, H, W, flip):
     sy = (C.c_long * n)(*[b[6] for b in branches])
     cs = (C.c_int * n)(*[b[7] for b in branches])
     ds = (C.c_int * n)(*[b[8] for b in branches])
-    rc = _lib.lib().cenet_dwconv3x3_nchw_multi_bf16(xs, sx, ws, ys, sy, cs, ds, n, B, H, W, int(flip), stream())
+    rc = _lib.lib().cenet_dwconv3x3_nchw_multi_bf16(xs, sx, ws, ys, sy, cs, ds, n, B, H, W, flip, stream())
     if rc == 2:  # CENET_EUNSUPPORTED
         return False
     _lib.check(rc, "cenet_dwconv3x3_nchw_multi_bf16")
@@ -663,14 +605,14 @@ def dw_wgrad_nchw_multi(branches, B, H, W):
 
 def dw_tok(x, w, bias, y, a, B, Cn, H, W, flip, act="none", slope=0.0):
     _chk(x, w, bias, y, a)
-    _call("cenet_dwconv3x3_tok_f32", x, w, bias, y, a, B, Cn, H, W, int(flip), ACT[act], float(slope))
+    _call("cenet_dwconv3x3_tok_f32", x, w, bias, y, a, B, Cn, H, W, flip, ACT[act], slope)
 
 
 def dw_tok_bwd_pre(x, g, w, bias, gu, dw, dbias, B, Cn, H, W, act, slope=0.0):
     """bf16 tokens: gu = g * act'(DW3x3(x) + bias), dw += gu (*) x, dbias += sum gu (pre-activation recomputed from x)."""
     _chk(x, g, w, bias, gu, dw, dbias)
     assert is_bf16(x) and is_bf16(g) and is_bf16(gu)
-    _call("cenet_dwconv3x3_tok_bwd_pre_bf16", x, g, w, bias, gu, dw, dbias, B, Cn, H, W, ACT[act], float(slope))
+    _call("cenet_dwconv3x3_tok_bwd_pre_bf16", x, g, w, bias, gu, dw, dbias, B, Cn, H, W, ACT[act], slope)
 
 
 def dw_tok_tiled(x):
@@ -691,7 +633,7 @@ def pvt_mlp_fwd(x, ln_g, ln_b, eps, w1, b1, wd, bd, w2, b2, bscale, y, B, H, W, 
     xn, mean, rstd, h, a = saved if saved is not None else (None,) * 5
     _chk(x, ln_g, ln_b, w1, b1, wd, bd, w2, b2, bscale, y, xn, mean, rstd, h, a)
     assert is_bf16(x) and is_bf16(y) and is_bf16(w1) and is_bf16(w2)
-    _call("cenet_pvt_mlp_fwd_bf16", x, ln_g, ln_b, float(eps), w1, b1, wd, bd, w2, b2, bscale, y, xn, mean, rstd, h, a, B, H, W,
+    _call("cenet_pvt_mlp_fwd_bf16", x, ln_g, ln_b, eps, w1, b1, wd, bd, w2, b2, bscale, y, xn, mean, rstd, h, a, B, H, W,
           Cn, HD)
 
 
@@ -703,16 +645,14 @@ def pvt_mlp_bwd(g, bscale, w1, w2, wd, bd, h, x, ln_g, mean, rstd, gu, dh, dx, d
     LayerNormBackward(dh . W1) with the affine gradients ADDED into dln_g / dln_b and the fc2 bias gradient (column sums of s_b g)
     into db2 (None: not wanted).  up_scale [B] + dxs: also dxs = up_scale_b * dx (see ops._prescaled_put)."""
     _chk(g, bscale, w1, w2, wd, bd, h, x, ln_g, mean, rstd, gu, dh, dx, dwd, dbd, dln_g, dln_b, db2, up_scale, dxs)
-    f = _lib.lib().cenet_pvt_mlp_bwd_ws_floats
-    f.restype = C.c_long
-    ws = torch.empty(int(f(B, H, W, Cn)), device=g.device, dtype=torch.float32)
+    ws = torch.empty(_lib.lib().cenet_pvt_mlp_bwd_ws_floats(B, H, W, Cn), device=g.device, dtype=torch.float32)
     _call("cenet_pvt_mlp_bwd_bf16", g, bscale, w1, w2, wd, bd, h, x, ln_g, mean, rstd, gu, dh, dx, up_scale, dxs, dwd, dbd, dln_g,
           dln_b, db2, ws, B, H, W, Cn, HD)
 
 
 def dw_wgrad_nchw(x, sxb, dy, sgb, dw, dbias, B, Cn, H, W, dil, x_off=0, g_off=0):
     _chk(x, dy, dw, dbias)
-    _call("cenet_dwconv3x3_wgrad_nchw_acc_f32", Ptr(x, x_off), L(sxb), Ptr(dy, g_off), L(sgb), dw, dbias, B, Cn, H, W, dil)
+    _call("cenet_dwconv3x3_wgrad_nchw_acc_f32", Ptr(x, x_off), sxb, Ptr(dy, g_off), sgb, dw, dbias, B, Cn, H, W, dil)
 
 
 def dw_wgrad_tok(x, dy, dw, dbias, B, Cn, H, W):
@@ -723,46 +663,46 @@ def dw_wgrad_tok(x, dy, dw, dbias, B, Cn, H, W):
 # ---- resampling ------------------------------------------------------------------------------------------
 def bilinear_fwd(x, sxb, y, syb, B, Cn, Hi, Wi, Ho, Wo, sh, sw, align):
     _chk(x, y)
-    _call("cenet_bilinear_fwd_f32", x, L(sxb), y, L(syb), B, Cn, Hi, Wi, Ho, Wo, float(sh), float(sw), int(align))
+    _call("cenet_bilinear_fwd_f32", x, sxb, y, syb, B, Cn, Hi, Wi, Ho, Wo, sh, sw, align)
 
 
 def bilinear_bwd(dy, sgb, dx, sdb, B, Cn, Hi, Wi, Ho, Wo, sh, sw, align, dx_add=None):
     """dx_add (laid out like dx, optional): added to dx by the kernel that writes it"""
     _chk(dy, dx, dx_add)
     if dx_add is None:
-        _call("cenet_bilinear_bwd_f32", dy, L(sgb), dx, L(sdb), B, Cn, Hi, Wi, Ho, Wo, float(sh), float(sw), int(align))
+        _call("cenet_bilinear_bwd_f32", dy, sgb, dx, sdb, B, Cn, Hi, Wi, Ho, Wo, sh, sw, align)
     else:
-        _call("cenet_bilinear_bwd_add_f32", dy, L(sgb), dx, L(sdb), dx_add, B, Cn, Hi, Wi, Ho, Wo, float(sh), float(sw), int(align))
+        _call("cenet_bilinear_bwd_add_f32", dy, sgb, dx, sdb, dx_add, B, Cn, Hi, Wi, Ho, Wo, sh, sw, align)
 
 
 def nearest2x_fwd(x, sxb, y, syb, B, Cn, Hi, Wi):
     _chk(x, y)
-    _call("cenet_nearest2x_fwd_f32", x, L(sxb), y, L(syb), B, Cn, Hi, Wi)
+    _call("cenet_nearest2x_fwd_f32", x, sxb, y, syb, B, Cn, Hi, Wi)
 
 
 def nearest2x_bwd(dy, sgb, dx, sdb, B, Cn, Hi, Wi):
     _chk(dy, dx)
-    _call("cenet_nearest2x_bwd_f32", dy, L(sgb), dx, L(sdb), B, Cn, Hi, Wi)
+    _call("cenet_nearest2x_bwd_f32", dy, sgb, dx, sdb, B, Cn, Hi, Wi)
 
 
 def avgpool_fwd(x, sxb, y, syb, B, Cn, Hi, Wi, Ho, Wo):
     _chk(x, y)
-    _call("cenet_adaptive_avgpool_fwd_f32", x, L(sxb), y, L(syb), B, Cn, Hi, Wi, Ho, Wo)
+    _call("cenet_adaptive_avgpool_fwd_f32", x, sxb, y, syb, B, Cn, Hi, Wi, Ho, Wo)
 
 
 def avgpool_bwd(dy, sgb, dx, sdb, B, Cn, Hi, Wi, Ho, Wo):
     _chk(dy, dx)
-    _call("cenet_adaptive_avgpool_bwd_f32", dy, L(sgb), dx, L(sdb), B, Cn, Hi, Wi, Ho, Wo)
+    _call("cenet_adaptive_avgpool_bwd_f32", dy, sgb, dx, sdb, B, Cn, Hi, Wi, Ho, Wo)
 
 
 def maxpool2_fwd(x, y, syb, scale, B, Cn, Hi, Wi):
     _chk(x, y, scale)
-    _call("cenet_maxpool2_fwd_f32", x, y, L(syb), scale, B, Cn, Hi, Wi)
+    _call("cenet_maxpool2_fwd_f32", x, y, syb, scale, B, Cn, Hi, Wi)
 
 
 def maxpool2_bwd(x, dy, sgb, dx, scale, dscale, B, Cn, Hi, Wi):
     _chk(x, dy, dx, scale, dscale)
-    _call("cenet_maxpool2_bwd_acc_f32", x, dy, L(sgb), dx, scale, dscale, B, Cn, Hi, Wi)
+    _call("cenet_maxpool2_bwd_acc_f32", x, dy, sgb, dx, scale, dscale, B, Cn, Hi, Wi)
 
 
 # ---- CCU / SRM ---------------------------------------------------------------------------------------------
@@ -808,11 +748,11 @@ _NO_SRM_FUSED = __import__("os").environ.get("CENET_NO_SRM_FUSED") is not None  
 
 
 def srm_fused_supported(B, H, W) -> bool:
-    return (not _NO_CHANLOC) and (not _NO_SRM_FUSED) and bool(_lib.lib().cenet_srm_fused_supported(int(B), int(H), int(W)))
+    return (not _NO_CHANLOC) and (not _NO_SRM_FUSED) and bool(_lib.lib().cenet_srm_fused_supported(B, H, W))
 
 
 def srm_parts(B, H, W) -> int:
-    return int(_lib.lib().cenet_srm_parts(int(B), int(H), int(W)))
+    return _lib.lib().cenet_srm_parts(B, H, W)
 
 
 def srm_conv_gelu_fwd(u, pwc, dwc, f, fa, part, B, H, W):
@@ -822,13 +762,13 @@ def srm_conv_gelu_fwd(u, pwc, dwc, f, fa, part, B, H, W):
 
 def gate_pix_bn_fwd(x, fa, part, G, fb, y, gamma, beta, eps, mean, var, rmean, rvar, momentum, nbt, B, Cn, HW):
     _chk(x, fa, part, fb, y, gamma, beta, mean, var, rmean, rvar)
-    _call("cenet_gate_pix_bn_fwd_f32", x, fa, part, G, fb, y, gamma, beta, float(eps), mean, var, rmean, rvar, float(momentum), nbt, B,
+    _call("cenet_gate_pix_bn_fwd_f32", x, fa, part, G, fb, y, gamma, beta, eps, mean, var, rmean, rvar, momentum, nbt, B,
           Cn, HW)
 
 
 def srm_conv_bn_bwd(u, dfb, fa, f, mean, var, eps, gamma, pwc, dwc, part2, du, dpwc, ddwc, dgamma, dbeta, B, H, W):
     _chk(u, dfb, fa, f, mean, var, gamma, pwc, dwc, part2, du, dpwc, ddwc, dgamma, dbeta)
-    _call("cenet_srm_conv_bn_bwd_acc_f32", u, dfb, fa, f, mean, var, float(eps), gamma, pwc, dwc, part2, du, dpwc, ddwc, dgamma,
+    _call("cenet_srm_conv_bn_bwd_acc_f32", u, dfb, fa, f, mean, var, eps, gamma, pwc, dwc, part2, du, dpwc, ddwc, dgamma,
           dbeta, B, H, W)
 
 
@@ -852,14 +792,14 @@ def transpose(x, sxb, y, syb, B, R, Cc, x_off=0, y_off=0, add=None):
     """y[b] = x[b]^T (+ add[b], laid out like y with batch stride syb)"""
     _chk(x, y, add)
     if add is None:
-        _call("cenet_transpose_f32", Ptr(x, x_off), L(sxb), Ptr(y, y_off), L(syb), B, R, Cc)
+        _call("cenet_transpose_f32", Ptr(x, x_off), sxb, Ptr(y, y_off), syb, B, R, Cc)
     else:
-        _call("cenet_transpose_add_f32", Ptr(x, x_off), L(sxb), Ptr(y, y_off), L(syb), add, B, R, Cc)
+        _call("cenet_transpose_add_f32", Ptr(x, x_off), sxb, Ptr(y, y_off), syb, add, B, R, Cc)
 
 
 def copy_batched(x, sxb, y, syb, B, n, accumulate=False, x_off=0, y_off=0):
     _chk(x, y)
-    _call("cenet_copy_batched_f32", Ptr(x, x_off), L(sxb), Ptr(y, y_off), L(syb), B, L(n), int(accumulate))
+    _call("cenet_copy_batched_f32", Ptr(x, x_off), sxb, Ptr(y, y_off), syb, B, n, accumulate)
 
 
 def cat_channels(parts, joined, B, HW, split=False):
@@ -867,8 +807,8 @@ def cat_channels(parts, joined, B, HW, split=False):
     assert 1 <= len(parts) <= 4
     _chk(joined, *parts)
     ps = list(parts) + [None] * (4 - len(parts))
-    cs = [int(t.shape[1]) for t in parts] + [0] * (4 - len(parts))
-    _call("cenet_cat_channels_f32", *ps, *cs, joined, B, L(HW), int(split))
+    cs = [t.shape[1] for t in parts] + [0] * (4 - len(parts))
+    _call("cenet_cat_channels_f32", *ps, *cs, joined, B, HW, split)
 
 
 def split_channels_add(parts, adds, joined, B, HW):
@@ -877,66 +817,66 @@ def split_channels_add(parts, adds, joined, B, HW):
     _chk(joined, *parts, *adds)
     ps = list(parts) + [None] * (4 - len(parts))
     ads = list(adds) + [None] * (4 - len(adds))
-    cs = [int(t.shape[1]) for t in parts] + [0] * (4 - len(parts))
-    _call("cenet_split_channels_add_f32", *ps, *ads, *cs, joined, B, L(HW))
+    cs = [t.shape[1] for t in parts] + [0] * (4 - len(parts))
+    _call("cenet_split_channels_add_f32", *ps, *ads, *cs, joined, B, HW)
 
 
 def add2_fwd(a, b, y, n):
     """y = a + b over n elements (the add join of a DSEB in skip_mode='add'), one launch"""
     _chk(a, b, y)
-    _call("cenet_add2_fwd_f32", a, b, y, L(n))
+    _call("cenet_add2_fwd_f32", a, b, y, n)
 
 
 def add2_bwd(g, ga, gb, da, db, n):
     """da = g + ga, db = g + gb (ga / gb None: g alone) over n elements, one launch reading g once"""
     _chk(g, da, db, *(t for t in (ga, gb) if t is not None))
-    _call("cenet_add2_bwd_f32", g, ga, gb, da, db, L(n))
+    _call("cenet_add2_bwd_f32", g, ga, gb, da, db, n)
 
 
 def im2col_tok(src, dst, B, H, W, C, K, stride, pad, inverse=False):
     _chk(src, dst)
-    _call("cenet_im2col_tok_f32", src, dst, B, H, W, C, K, stride, pad, int(inverse))
+    _call("cenet_im2col_tok_f32", src, dst, B, H, W, C, K, stride, pad, inverse)
 
 
 def patch_tok(src, dst, B, Ho, Wo, C, S, inverse=False):
     """Space-to-depth of a token map (inverse: patch rows back to tokens); pvtv2.py:93-95 kernel == stride conv."""
     _chk(src, dst)
-    _call("cenet_patch_tok_f32", src, dst, B, Ho, Wo, C, S, int(inverse))
+    _call("cenet_patch_tok_f32", src, dst, B, Ho, Wo, C, S, inverse)
 
 
 def scale_batch(x, s, y, B, n):
     _chk(x, s, y)
-    _call("cenet_scale_batch_f32", x, s, y, B, L(n))
+    _call("cenet_scale_batch_f32", x, s, y, B, n)
 
 
 def act_fwd(x, y, n, act, slope=0.0):
     _chk(x, y)
-    _call("cenet_act_fwd_f32", x, y, L(n), ACT[act], float(slope))
+    _call("cenet_act_fwd_f32", x, y, n, ACT[act], slope)
 
 
 def act_bwd(pre, dy, dx, n, act, slope=0.0):
     _chk(pre, dy, dx)
-    _call("cenet_act_bwd_f32", pre, dy, dx, L(n), ACT[act], float(slope))
+    _call("cenet_act_bwd_f32", pre, dy, dx, n, ACT[act], slope)
 
 
 def silu_mul_fwd(a, b, y, n):
     _chk(a, b, y)
-    _call("cenet_silu_mul_fwd_f32", a, b, y, L(n))
+    _call("cenet_silu_mul_fwd_f32", a, b, y, n)
 
 
 def silu_mul_bwd(a, b, dy, da, db, n):
     _chk(a, b, dy, da, db)
-    _call("cenet_silu_mul_bwd_f32", a, b, dy, da, db, L(n))
+    _call("cenet_silu_mul_bwd_f32", a, b, dy, da, db, n)
 
 
 def mix_fwd(x, p, w, z, n):
     _chk(x, p, w, z)
-    _call("cenet_mix_fwd_f32", x, p, w, z, L(n))
+    _call("cenet_mix_fwd_f32", x, p, w, z, n)
 
 
 def mix_bwd(x, p, w, dz, dx, dp, dw, n):
     _chk(x, p, w, dz, dx, dp, dw)
-    _call("cenet_mix_bwd_acc_f32", x, p, w, dz, dx, dp, dw, L(n))
+    _call("cenet_mix_bwd_acc_f32", x, p, w, dz, dx, dp, dw, n)
 
 
 def scale_residual_fwd(x, y, ls, out, B, Cn, HW):
@@ -951,41 +891,41 @@ def scale_chan(g, ls, out, B, Cn, HW):
 
 def chan_dot(a, sab, b, sbb, out, B, Cn, HW):
     _chk(a, b, out)
-    _call("cenet_chan_dot_acc_f32", a, L(sab), b, L(sbb), out, B, Cn, HW)
+    _call("cenet_chan_dot_acc_f32", a, sab, b, sbb, out, B, Cn, HW)
 
 
 def col_sum(a, out, R, Cn):
     _chk(a, out)
-    _call("cenet_col_sum_acc_f32", a, out, L(R), Cn)
+    _call("cenet_col_sum_acc_f32", a, out, R, Cn)
 
 
 def add_act_fwd(a, b, out, n, act="none", slope=0.0):
     _chk(a, b, out)
-    _call("cenet_add_act_fwd_f32", a, b, out, L(n), ACT[act], float(slope))
+    _call("cenet_add_act_fwd_f32", a, b, out, n, ACT[act], slope)
 
 
 def lrelu_bwd_from_out(out, dy, dx, n, slope):
     _chk(out, dy, dx)
-    _call("cenet_lrelu_bwd_from_out_f32", out, dy, dx, L(n), float(slope))
+    _call("cenet_lrelu_bwd_from_out_f32", out, dy, dx, n, slope)
 
 
 def dseb_combine_fwd(y, rs, n, w, diff, ycoef, z, B, Cn, HW):
     _chk(y, w, diff, z, *rs)
     r = list(rs) + [None] * (3 - len(rs))
-    _call("cenet_dseb_combine_fwd_f32", y, r[0], r[1], r[2], n, w, diff, float(ycoef), z, B, Cn, HW)
+    _call("cenet_dseb_combine_fwd_f32", y, r[0], r[1], r[2], n, w, diff, ycoef, z, B, Cn, HW)
 
 
 def dseb_combine_bwd(y, rs, n, w, diff, ycoef, dz, dy, drs, ddiff, dw, B, Cn, HW):
     _chk(y, w, diff, dz, dy, ddiff, dw, *rs, *drs)
     r = list(rs) + [None] * (3 - len(rs))
     d = list(drs) + [None] * (3 - len(drs))
-    _call("cenet_dseb_combine_bwd_acc_f32", y, r[0], r[1], r[2], n, w, diff, float(ycoef), dz, dy, d[0], d[1], d[2], ddiff, dw, B,
+    _call("cenet_dseb_combine_bwd_acc_f32", y, r[0], r[1], r[2], n, w, diff, ycoef, dz, dy, d[0], d[1], d[2], ddiff, dw, B,
           Cn, HW)
 
 
 def diffattn_lambda_fwd(q1, k1, q2, k2, lam0, lam3, hd):
     _chk(q1, k1, q2, k2, lam3)
-    _call("cenet_diffattn_lambda_fwd_f32", q1, k1, q2, k2, float(lam0), lam3, hd)
+    _call("cenet_diffattn_lambda_fwd_f32", q1, k1, q2, k2, lam0, lam3, hd)
 
 
 def diffattn_lambda_bwd(q1, k1, q2, k2, lam3, dlam, dq1, dk1, dq2, dk2, hd):
@@ -995,33 +935,33 @@ def diffattn_lambda_bwd(q1, k1, q2, k2, lam3, dlam, dq1, dk1, dq2, dk2, hd):
 
 def diffattn_combine_fwd(U, lam3, out, B, H, N, dv, eps, post):
     _chk(U, lam3, out)
-    _call("cenet_diffattn_combine_fwd_f32", U, lam3, out, B, H, N, dv, float(eps), float(post))
+    _call("cenet_diffattn_combine_fwd_f32", U, lam3, out, B, H, N, dv, eps, post)
 
 
 def diffattn_combine_bwd(U, lam3, dout, dU, dlam, B, H, N, dv, eps, post):
     _chk(U, lam3, dout, dU, dlam)
-    _call("cenet_diffattn_combine_bwd_acc_f32", U, lam3, dout, dU, dlam, B, H, N, dv, float(eps), float(post))
+    _call("cenet_diffattn_combine_bwd_acc_f32", U, lam3, dout, dU, dlam, B, H, N, dv, eps, post)
 
 
 # ---- loss / optimiser --------------------------------------------------------------------------------------
 def dice_ce_fwd(logits, labels, acc, loss, B, K, HW, w_dice, w_ce):
     _chk(logits, labels, acc, loss)
-    _call("cenet_dice_ce_fwd_f32", logits, labels, acc, loss, B, K, HW, float(w_dice), float(w_ce))
+    _call("cenet_dice_ce_fwd_f32", logits, labels, acc, loss, B, K, HW, w_dice, w_ce)
 
 
 def dice_ce_bwd(logits, labels, acc, gout, dlogits, B, K, HW, w_dice, w_ce):
     _chk(logits, labels, acc, gout, dlogits)
-    _call("cenet_dice_ce_bwd_f32", logits, labels, acc, gout, dlogits, B, K, HW, float(w_dice), float(w_ce))
+    _call("cenet_dice_ce_bwd_f32", logits, labels, acc, gout, dlogits, B, K, HW, w_dice, w_ce)
 
 
 def seg_loss_fwd(logits, labels, acc, loss, B, K, H, W, w_dice, w_ce, w_bd):
     _chk(logits, labels, acc, loss)
-    _call("cenet_seg_loss_fwd_f32", logits, labels, acc, loss, B, K, H, W, float(w_dice), float(w_ce), float(w_bd))
+    _call("cenet_seg_loss_fwd_f32", logits, labels, acc, loss, B, K, H, W, w_dice, w_ce, w_bd)
 
 
 def seg_loss_bwd(logits, labels, acc, gout, dlogits, B, K, H, W, w_dice, w_ce, w_bd):
     _chk(logits, labels, acc, gout, dlogits)
-    _call("cenet_seg_loss_bwd_f32", logits, labels, acc, gout, dlogits, B, K, H, W, float(w_dice), float(w_ce), float(w_bd))
+    _call("cenet_seg_loss_bwd_f32", logits, labels, acc, gout, dlogits, B, K, H, W, w_dice, w_ce, w_bd)
 
 
 def argmax_counts(logits, labels, pred, counts, B, K, HW):
@@ -1052,7 +992,7 @@ def edt_sq_raw(feat_u8, match, tmp_i32, d2_i32, D, H, W):
     _chk(feat_u8, tmp_i32, d2_i32)
     if not edt_supported(D, H, W):
         raise ValueError(f"the distance transform needs D^2 + H^2 + W^2 < 2^31, got {(D, H, W)}")
-    _call("cenet_edt_sq_u8", feat_u8, int(match), tmp_i32, d2_i32, D, H, W)
+    _call("cenet_edt_sq_u8", feat_u8, match, tmp_i32, d2_i32, D, H, W)
 
 
 def edt_sq(feat_u8: torch.Tensor) -> torch.Tensor:
@@ -1074,33 +1014,31 @@ def label_borders(pred_f32, gt_f32, border_pred_u8, border_gt_u8, table_i32, K, 
 
 def border_count(bl_u8, match, n, counts_i32):
     _chk(bl_u8, counts_i32)
-    _call("cenet_border_count_u8", bl_u8, int(match), L(n), counts_i32)
+    _call("cenet_border_count_u8", bl_u8, match, n, counts_i32)
 
 
 def border_gather(bl_u8, match, D, H, W, offs_i32, src_i32, out_i32):
     """src_i32 None: out gets the (z, y, x) rows of the matching voxels; else src at those voxels — both in C order"""
     _chk(bl_u8, offs_i32, src_i32, out_i32)
-    _call("cenet_border_gather_i32", bl_u8, int(match), D, H, W, offs_i32, src_i32, out_i32)
+    _call("cenet_border_gather_i32", bl_u8, match, D, H, W, offs_i32, src_i32, out_i32)
 
 
 def sgd_step(p, g, buf, hyper5, n, shadow=None):
     """shadow: bf16 copy of the parameters, rewritten by the same kernel (the GEMM operand of the throughput mode)"""
     _chk(p, g, buf, hyper5, shadow)
     if shadow is None:
-        _call("cenet_sgd_step_f32", p, g, buf, hyper5, L(n))
+        _call("cenet_sgd_step_f32", p, g, buf, hyper5, n)
     else:
-        rc = _lib.lib().cenet_sgd_step_shadow_f32(P(p), P(g), P(buf), P(hyper5), L(n), P(shadow), stream())
-        _lib.check(rc, "cenet_sgd_step_shadow_f32")
+        _launch("cenet_sgd_step_shadow_f32", p, g, buf, hyper5, n, shadow)
 
 
 def adam_step(p, g, exp_avg, exp_avg_sq, hyper12, n, shadow=None):
     """fused Adam / AdamW update (hyper12: include/cenet_hip.h); shadow: bf16 copy of the parameters, rewritten in the same pass"""
     _chk(p, g, exp_avg, exp_avg_sq, hyper12, shadow)
     if shadow is None:
-        _call("cenet_adam_step_f32", p, g, exp_avg, exp_avg_sq, hyper12, L(n))
+        _call("cenet_adam_step_f32", p, g, exp_avg, exp_avg_sq, hyper12, n)
     else:
-        rc = _lib.lib().cenet_adam_step_shadow_f32(P(p), P(g), P(exp_avg), P(exp_avg_sq), P(hyper12), L(n), P(shadow), stream())
-        _lib.check(rc, "cenet_adam_step_shadow_f32")
+        _launch("cenet_adam_step_shadow_f32", p, g, exp_avg, exp_avg_sq, hyper12, n, shadow)
 
 
 def cast(x: torch.Tensor, dtype) -> torch.Tensor:
@@ -1111,7 +1049,7 @@ def cast(x: torch.Tensor, dtype) -> torch.Tensor:
     x = x if x.is_contiguous() else x.contiguous()
     y = torch.empty(x.shape, device=x.device, dtype=dtype)
     name = "cenet_cast_f32_to_bf16" if dtype == BF16 else "cenet_cast_bf16_to_f32"
-    _lib.check(getattr(_lib.lib(), name)(P(x), P(y), L(x.numel()), stream()), name)
+    _launch(name, x, y, x.numel())
     return y
 
 
@@ -1120,16 +1058,15 @@ def cast_clear(x: torch.Tensor, y: torch.Tensor, bias: Optional[torch.Tensor] = 
     _chk(x, y, bias)
     assert x.dtype == torch.float32 and y.dtype == BF16 and x.numel() == y.numel()
     if bias is None:
-        _lib.check(_lib.lib().cenet_cast_clear_f32_to_bf16(P(x), P(y), L(x.numel()), stream()), "cenet_cast_clear_f32_to_bf16")
+        _launch("cenet_cast_clear_f32_to_bf16", x, y, x.numel())
     else:
-        _lib.check(_lib.lib().cenet_cast_clear_bias_f32_to_bf16(P(x), P(y), P(bias), C.c_int(bias.numel()), L(x.numel()), stream()),
-                   "cenet_cast_clear_bias_f32_to_bf16")
+        _launch("cenet_cast_clear_bias_f32_to_bf16", x, y, bias, bias.numel(), x.numel())
 
 
 def cast_into(x: torch.Tensor, y: torch.Tensor):
     name = "cenet_cast_f32_to_bf16" if y.dtype == BF16 else "cenet_cast_bf16_to_f32"
     assert x.dtype != y.dtype and x.numel() == y.numel() and x.is_contiguous() and y.is_contiguous()
-    _lib.check(getattr(_lib.lib(), name)(P(x), P(y), L(x.numel()), stream()), name)
+    _launch(name, x, y, x.numel())
 
 
 def wq(W: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
@@ -1163,14 +1100,14 @@ def zero_(t: torch.Tensor):
     if nbytes == 0:
         return t
     if nbytes % 4 == 0 and t.data_ptr() % 4 == 0:
-        _lib.check(_lib.lib().cenet_zero_f32(P(t), L(nbytes // 4), stream()), "cenet_zero_f32")
+        _launch("cenet_zero_f32", t, nbytes // 4)
     else:  # a bf16 tensor with an odd element count / an odd-element view: head and tail bytes handled by the kernel
-        _lib.check(_lib.lib().cenet_zero_bytes(P(t), L(nbytes), stream()), "cenet_zero_bytes")
+        _launch("cenet_zero_bytes", t, nbytes)
     return t
 
 
 def conv_direct_supported(Cin: int, Cout: int, k: int, stride: int, pad: int) -> bool:
-    return bool(_lib.lib().cenet_conv_direct_supported(int(Cin), int(Cout), int(k), int(stride), int(pad)))
+    return bool(_lib.lib().cenet_conv_direct_supported(Cin, Cout, k, stride, pad))
 
 
 def conv_direct(x, w, y, B, Cin, Cout, H, W, k, dgrad):
@@ -1178,81 +1115,74 @@ def conv_direct(x, w, y, B, Cin, Cout, H, W, k, dgrad):
     dgrad: x=dY, w=forward weight, y=dX."""
     _chk(x, w, y)
     assert x.dtype == BF16 and y.dtype == BF16 and w.dtype == torch.float32
-    rc = _lib.lib().cenet_conv_direct_bf16(P(x), P(w), P(y), B, Cin, Cout, H, W, k, int(dgrad), stream())
-    _lib.check(rc, "cenet_conv_direct_bf16")
+    _launch("cenet_conv_direct_bf16", x, w, y, B, Cin, Cout, H, W, k, dgrad)
 
 
 def conv_c1_supported(Cin: int, Cout: int, k: int, stride: int, pad: int) -> bool:
-    return bool(_lib.lib().cenet_conv_c1_supported(int(Cin), int(Cout), int(k), int(stride), int(pad)))
+    return bool(_lib.lib().cenet_conv_c1_supported(Cin, Cout, k, stride, pad))
 
 
 def conv_c1_fwd(x, w, y, B, Cout, H, W, k):
     """one-channel bf16 image -> Cout <= 32 channels, stride 1, same padding (conv_c1.hip)"""
     _chk(x, w, y)
     assert x.dtype == BF16 and y.dtype == BF16 and w.dtype == torch.float32
-    _lib.check(_lib.lib().cenet_conv_c1_fwd_bf16(P(x), P(w), P(y), B, Cout, H, W, k, stream()), "cenet_conv_c1_fwd_bf16")
+    _launch("cenet_conv_c1_fwd_bf16", x, w, y, B, Cout, H, W, k)
 
 
 def conv_c1_wgrad(x, dy, dw, B, Cout, H, W, k):
     _chk(x, dy, dw)
     assert x.dtype == BF16 and dy.dtype == BF16 and dw.dtype == torch.float32
-    _lib.check(_lib.lib().cenet_conv_c1_wgrad_bf16(P(x), P(dy), P(dw), B, Cout, H, W, k, stream()), "cenet_conv_c1_wgrad_bf16")
+    _launch("cenet_conv_c1_wgrad_bf16", x, dy, dw, B, Cout, H, W, k)
 
 
 def pw_fewout_supported(Cin: int, Cout: int) -> bool:
-    return bool(_lib.lib().cenet_pw_fewout_supported(int(Cin), int(Cout)))
+    return bool(_lib.lib().cenet_pw_fewout_supported(Cin, Cout))
 
 
 def pw_fewout_wgrad_supported(Cin: int, Cout: int) -> bool:
-    return bool(_lib.lib().cenet_pw_fewout_wgrad_supported(int(Cin), int(Cout)))
+    return bool(_lib.lib().cenet_pw_fewout_wgrad_supported(Cin, Cout))
 
 
 def pw_fewout_fwd(x, W, bias, y, B, Cin, Cout, HW):
     """64 -> few channels 1x1 conv with bias on bf16 tensors (conv_c1.hip); W: bf16 [Cout, 64]"""
     _chk(x, W, bias, y)
     assert x.dtype == BF16 and y.dtype == BF16 and W.dtype == BF16
-    _lib.check(_lib.lib().cenet_pw_fewout_fwd_bf16(P(x), P(W), P(bias) if bias is not None else None, P(y), B, Cin, Cout, L(HW),
-                                                   stream()), "cenet_pw_fewout_fwd_bf16")
+    _launch("cenet_pw_fewout_fwd_bf16", x, W, bias, y, B, Cin, Cout, HW)
 
 
 def pw_fewout_dgrad(dy, W, dx, B, Cin, Cout, HW):
     _chk(dy, W, dx)
     assert dy.dtype == BF16 and dx.dtype == BF16 and W.dtype == BF16
-    _lib.check(_lib.lib().cenet_pw_fewout_dgrad_bf16(P(dy), P(W), P(dx), B, Cin, Cout, L(HW), stream()), "cenet_pw_fewout_dgrad_bf16")
+    _launch("cenet_pw_fewout_dgrad_bf16", dy, W, dx, B, Cin, Cout, HW)
 
 
 def pw_fewout_wgrad(x, dy, dW, dbias, B, Cin, Cout, HW):
     _chk(x, dy, dW, dbias)
     assert x.dtype == BF16 and dy.dtype == BF16 and dW.dtype == torch.float32
-    _lib.check(_lib.lib().cenet_pw_fewout_wgrad_bf16(P(x), P(dy), P(dW), P(dbias) if dbias is not None else None, B, Cin, Cout,
-                                                     L(HW), stream()), "cenet_pw_fewout_wgrad_bf16")
+    _launch("cenet_pw_fewout_wgrad_bf16", x, dy, dW, dbias, B, Cin, Cout, HW)
 
 
 def pw_small_supported(G: int) -> bool:
-    return bool(_lib.lib().cenet_pw_small_supported(int(G)))
+    return bool(_lib.lib().cenet_pw_small_supported(G))
 
 
 def pw_small(x, W, y, B, groups, G, HW, transpose=False):
     """groups x (G x G) bias-free 1x1 convs on bf16 NCHW tensors, G <= 40 (conv_c1.hip); W: bf16 [groups, G, G]"""
     _chk(x, W, y)
     assert x.dtype == BF16 and y.dtype == BF16 and W.dtype == BF16
-    _lib.check(_lib.lib().cenet_pw_small_bf16(P(x), P(W), P(y), B, groups, G, L(HW), int(transpose), stream()),
-               "cenet_pw_small_bf16")
+    _launch("cenet_pw_small_bf16", x, W, y, B, groups, G, HW, transpose)
 
 
 def conv_wgrad_direct_supported(Cin: int, Cout: int, k: int, stride: int, pad: int) -> bool:
-    return bool(_lib.lib().cenet_conv_wgrad_direct_supported(int(Cin), int(Cout), int(k), int(stride), int(pad)))
+    return bool(_lib.lib().cenet_conv_wgrad_direct_supported(Cin, Cout, k, stride, pad))
 
 
 def conv_wgrad_direct(x, dy, dw, B, Cin, Cout, H, W, k):
     """bf16-operand direct weight gradient (LDS tiles of dY and the X halo, funnel-shifted tap windows): dw += dY (*) x."""
     _chk(x, dy, dw)
     assert x.dtype == BF16 and dy.dtype == BF16 and dw.dtype == torch.float32
-    fn = _lib.lib().cenet_conv_wgrad_direct_ws_floats
-    fn.restype = C.c_long
-    ws = torch.empty(int(fn(int(Cin), int(Cout), int(k))), device=x.device, dtype=torch.float32)
-    rc = _lib.lib().cenet_conv_wgrad_direct_bf16(P(x), P(dy), P(dw), P(ws), B, Cin, Cout, H, W, k, stream())
-    _lib.check(rc, "cenet_conv_wgrad_direct_bf16")
+    ws = torch.empty(_lib.lib().cenet_conv_wgrad_direct_ws_floats(Cin, Cout, k), device=x.device, dtype=torch.float32)
+    _launch("cenet_conv_wgrad_direct_bf16", x, dy, dw, ws, B, Cin, Cout, H, W, k)
 
 
 # ---- precision mode ------------------------------------------------------------------------------------------------
@@ -1282,10 +1212,8 @@ def augment_acdc(pool_img, pool_lab, tab, dp, stage_img, stage_lab, stage_stride
     assert stage_img.dtype == torch.float64 and stage_lab.dtype == torch.uint8 and out_img.dtype == torch.float32
     for t in (pool_img, pool_lab, tab, dp, stage_img, stage_lab, out_img, out_lab):
         assert t.is_contiguous()
-    rc = _lib.lib().cenet_augment_acdc(P(pool_img), P(pool_lab), P(tab), P(dp), P(stage_img), P(stage_lab), L(stage_stride),
-                                       C.c_int(max_h), C.c_int(max_w), P(out_img), P(out_lab), C.c_int(B), C.c_int(OH), C.c_int(OW),
-                                       stream())
-    _lib.check(rc, "cenet_augment_acdc")
+    _launch("cenet_augment_acdc", pool_img, pool_lab, tab, dp, stage_img, stage_lab, stage_stride, max_h, max_w, out_img, out_lab,
+            B, OH, OW)
 
 
 _SPLINE_POLE = math.sqrt(3.0) - 2.0  # the cubic B-spline prefilter's pole (scipy ni_splines)
@@ -1303,11 +1231,9 @@ def vol_resize_cubic(src, stage, out, n, H, W, PH, PW, normalize=None):
     assert src.dtype == torch.float32 and out.dtype == torch.float32 and stage.dtype == torch.float64
     assert src.is_contiguous() and out.is_contiguous() and stage.is_contiguous()
     assert src.numel() >= n * H * W and stage.numel() >= n * H * W and out.numel() == n * PH * PW
-    mean, std = (float(normalize[0]), float(normalize[1])) if normalize is not None else (0.0, 1.0)
-    rc = _lib.lib().cenet_vol_resize_cubic(P(src), P(stage), P(out), C.c_int(n), C.c_int(H), C.c_int(W), C.c_int(PH), C.c_int(PW),
-                                           C.c_double(_SPLINE_POLE ** (H - 1)), C.c_double(_SPLINE_POLE ** (W - 1)),
-                                           C.c_int(int(normalize is not None)), C.c_float(mean), C.c_float(std), stream())
-    _lib.check(rc, "cenet_vol_resize_cubic")
+    mean, std = normalize if normalize is not None else (0.0, 1.0)
+    _launch("cenet_vol_resize_cubic", src, stage, out, n, H, W, PH, PW, _SPLINE_POLE ** (H - 1), _SPLINE_POLE ** (W - 1),
+            normalize is not None, mean, std)
 
 
 def argmax_resize_counts(logits, labels, pred, counts, n, K, PH, PW, H, W):
@@ -1326,6 +1252,4 @@ def layernorm_fwd_acc(acc, bias, xpre, gamma, beta, y, mean, rstd, rows, Cn, eps
     """cenet_layernorm_fwd_acc_bf16: LayerNorm straight from a split-K fp32 accumulator (+ bias); acc is zero afterwards"""
     _chk(acc, bias, xpre, gamma, beta, y, mean, rstd)
     assert acc.dtype == torch.float32 and xpre.dtype == BF16 and y.dtype == BF16
-    rc = _lib.lib().cenet_layernorm_fwd_acc_bf16(P(acc), P(bias), P(xpre), P(gamma), P(beta), P(y), P(mean), P(rstd), C.c_int(rows),
-                                                 C.c_int(Cn), C.c_float(eps), stream())
-    _lib.check(rc, "cenet_layernorm_fwd_acc_bf16")
+    _launch("cenet_layernorm_fwd_acc_bf16", acc, bias, xpre, gamma, beta, y, mean, rstd, rows, Cn, eps)

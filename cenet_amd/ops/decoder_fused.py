@@ -518,8 +518,7 @@ def res_tail_img_pool_supported(x2, img, w3, bn2, bn3, w) -> bool:
     return bool(bn2.training and bn3.training and _bf(x2) and _bf(img) and img.dim() == 4 and img.shape[1] == 1
                 and not img.requires_grad and tuple(w3.shape[1:]) == (1, 1, 1) and w3.shape[0] == x2.shape[1]
                 and img.shape[0] == x2.shape[0] and tuple(img.shape[2:]) == tuple(x2.shape[2:]) and w.numel() == x2.shape[1]
-                and x2.data_ptr() % 16 == 0 and img.data_ptr() % 16 == 0
-                and kern._lib.lib().cenet_res_tail_supported(int(x2.shape[2]), int(x2.shape[3]))
+                and img.data_ptr() % 16 == 0 and kern.res_tail_supported(x2, x2)  # (x3 is not materialised here)
                 and os.environ.get("CENET_RES_TAIL_FUSED", "1") not in ("0", "x3"))
 
 

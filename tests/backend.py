@@ -20,7 +20,7 @@ def use_sim():
     if _SIM is None:
         from build_sim import build_sim
         # CENET_SIM_SANITIZE=1: the UndefinedBehaviorSanitizer build of the same sources (sanitizers run on the CPU build only)
-        _SIM = ctypes.CDLL(build_sim(sanitize=os.environ.get("CENET_SIM_SANITIZE") == "1"))
+        _SIM = _lib.bind(ctypes.CDLL(build_sim(sanitize=os.environ.get("CENET_SIM_SANITIZE") == "1")))
     _lib._LIB = _SIM
     _lib._HOSTSIM = True
     return torch.device("cpu")

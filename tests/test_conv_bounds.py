@@ -663,7 +663,7 @@ def test_tiled_tok_refuses_flip_with_bias_or_activation(dev):
     y, a = torch.zeros_like(x), torch.zeros_like(x)
     w, b = torch.zeros(8, 9, device=dev), torch.zeros(8, device=dev)
     args = lambda bias, act_out: (kern.P(x), kern.P(w), kern.P(bias), kern.P(y), kern.P(act_out), 1, 8, 7, 7, 1, 0,  # noqa: E731
-                                  kern.C.c_float(0.0), kern.stream())
+                                  0.0, kern.stream())
     assert _lib.lib().cenet_dwconv3x3_tok_bf16(*args(b, None)) == 2      # CENET_EUNSUPPORTED
     assert _lib.lib().cenet_dwconv3x3_tok_bf16(*args(None, a)) == 2
     assert _lib.lib().cenet_dwconv3x3_tok_bf16(*args(None, None)) == 0

@@ -258,7 +258,6 @@ def test_zero_fill_of_odd_sized_bf16_buffers(dev, n, off):
 def test_dpp_wave_reductions(dev):
     """common.h wave_sum_dpp / wave_max_dpp / wave_min_i_dpp (round 5: the wave reductions of every kernel): against numpy on
     random, all-negative and single-outlier waves; on the host checker the same entry runs the shuffle forms."""
-    import ctypes as C
     import numpy as np
     from cenet_amd import _lib, kern
     g = torch.Generator().manual_seed(4)
@@ -272,7 +271,7 @@ def test_dpp_wave_reductions(dev):
     xd = x.to(dev)
     sums, maxs = torch.empty(2 * nw).to(dev), torch.empty(2 * nw).to(dev)
     mins = torch.empty(2 * nw, dtype=torch.int32).to(dev)
-    rc = _lib.lib().cenet_selftest_wave_reduce(kern.P(xd), kern.P(sums), kern.P(maxs), kern.P(mins), C.c_int(nw), kern.stream())
+    rc = _lib.lib().cenet_selftest_wave_reduce(kern.P(xd), kern.P(sums), kern.P(maxs), kern.P(mins), nw, kern.stream())
     assert rc == 0
     if dev.type != "cpu":
         torch.cuda.synchronize()

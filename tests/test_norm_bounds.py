@@ -450,8 +450,8 @@ def run_bn_bwd(d, regime, cls, dt, B, C, HW, act="none", lead=8, dlead=8, Ctot=N
             (dgb, R.as_exp(dgb, gl, (C,), (1,), o["dgamma"], add=True, dims=("channel",), kernel=name + " dgamma")),
             (dbb, R.as_exp(dbb, bl, (C,), (1,), o["dbeta"], add=True, dims=("channel",), kernel=name + " dbeta"))]
     if add == "wide":  # (kern.bn_bwd takes a contiguous dx_add: the strided one goes through the entry point itself)
-        kern._call("cenet_bn_bwd_add_acc_f32", kern.Ptr(gb, go), kern.L(sgb), kern.Ptr(xb, xo), kern.L(sxb), kern.Ptr(dxb, do),
-                   kern.L(sdb), kern.Ptr(ab, ao), kern.L(sab), mean, var, BN_EPS, gd, bd, kern.ACT[act], SLOPE, B, C, HW, ws,
+        kern._call("cenet_bn_bwd_add_acc_f32", kern.Ptr(gb, go), sgb, kern.Ptr(xb, xo), sxb, kern.Ptr(dxb, do),
+                   sdb, kern.Ptr(ab, ao), sab, mean, var, BN_EPS, gd, bd, kern.ACT[act], SLOPE, B, C, HW, ws,
                    kern.Ptr(dgb, gl), kern.Ptr(dbb, bl))
     else:
         kern.bn_bwd(gb[go:], sgb, xb[xo:], sxb, dxb[do:], sdb, mean, var, BN_EPS, gd, bd, act, SLOPE, B, C, HW, ws, dgb[gl:], dbb[bl:],
@@ -727,7 +727,7 @@ def test_norm_bound_outlier_first(dev, case):
 def test_layernorm_backward_refuses_wide_rows(dev):
     x = torch.zeros(2 * 516, device=dev)
     v = torch.zeros(516, device=dev)
-    rc = _lib.lib().cenet_layernorm_bwd_add_acc_f32(kern.P(x), kern.P(x), kern.P(v), kern.P(v), kern.P(v), kern.P(None), kern.P(x),
+    rc = _lib.lib().cenet_layernorm_bwd_add_acc_f32(kern.P(x), kern.P(x), kern.P(v), kern.P(v), kern.P(v), None, kern.P(x),
                                                     kern.P(v), kern.P(v), 2, 516, kern.stream())
     assert rc == 2  # CENET_EUNSUPPORTED
 
