@@ -964,6 +964,30 @@ def seg_loss_bwd(logits, labels, acc, gout, dlogits, B, K, H, W, w_dice, w_ce, w
     _call("cenet_seg_loss_bwd_f32", logits, labels, acc, gout, dlogits, B, K, H, W, w_dice, w_ce, w_bd)
 
 
+def seg_loss_ex_ws_floats(B, K, H, W) -> int:
+    """floats of workspace cenet_seg_loss_ex_fwd needs: the compact sums plus one row of partials per forward workgroup"""
+    n = _lib.lib().cenet_seg_loss_ex_ws_floats(B, K, H, W)
+    if n <= 0:
+        raise ValueError(f"seg_loss_ex: unsupported shape B={B} K={K} H={H} W={W} (K <= 16)")
+    return n
+
+
+def seg_loss_ex_fwd(logits, labels, cw, ws, loss, B, K, H, W, w_dice, w_ce, w_bd, w_jac, smooth, ignore_index, from_probs):
+    """cw: [2K] fp32 class weights (Dice then CE) or None; ignore_index: int or None"""
+    _chk(logits, labels, cw, ws, loss)
+    has_ignore, ign = (0, 0) if ignore_index is None else (1, int(ignore_index))
+    _call("cenet_seg_loss_ex_fwd_f32", logits, labels, cw, ws, ws.numel(), loss, B, K, H, W, w_dice, w_ce, w_bd, w_jac, smooth,
+          has_ignore, ign, int(from_probs))
+
+
+def seg_loss_ex_bwd(logits, labels, cw, ws, gout, dlogits, B, K, H, W, w_dice, w_ce, w_bd, w_jac, smooth, ignore_index,
+                    from_probs):
+    _chk(logits, labels, cw, ws, gout, dlogits)
+    has_ignore, ign = (0, 0) if ignore_index is None else (1, int(ignore_index))
+    _call("cenet_seg_loss_ex_bwd_f32", logits, labels, cw, ws, gout, dlogits, B, K, H, W, w_dice, w_ce, w_bd, w_jac, smooth,
+          has_ignore, ign, int(from_probs))
+
+
 def argmax_counts(logits, labels, pred, counts, B, K, HW):
     _chk(logits, labels, pred)
     _call("cenet_argmax_counts_f32", logits, labels, pred, counts, B, K, HW)

@@ -3,25 +3,31 @@
 Dice, cross-entropy and BoundaryDoULoss (core.py:44-131) are terms of ONE fused HIP kernel each way
 (cenet_amd.ops.dice_ce_loss): the per-class sums they share are accumulated once, the boundary-pixel counts of
 BoundaryDoULoss come from the same pass over the labels, and the backward is a single kernel for any weighting.
+
+Class weights (DiceLoss.forward's `weight`, CrossEntropyLoss's `weight`), `ignore_index`, JaccardLoss (core.py:134-158) and
+DiceLoss(softmax=False) go through cenet_amd.ops.seg_loss (csrc/seg_loss_ex.hip): the same one pass, partial sums stored per
+workgroup and added in a fixed order instead of float atomics.  A call that uses none of them keeps the first path.
 """
 from __future__ import annotations
 
+import torch
 import torch.nn as nn
 
 from . import ops
 
 
 class DiceLoss(nn.Module):
-    """core.py:44-80 with softmax=True, weight=None."""
+    """core.py:44-80.  `weight`: K numbers (uploaded once per set of values) or a device tensor; softmax=False: `inputs`
+    already holds probabilities and receives the gradient directly."""
 
     def __init__(self, n_classes):
         super().__init__()
         self.n_classes = n_classes
 
     def forward(self, inputs, target, weight=None, softmax=False):
-        if not softmax or weight is not None:
-            raise NotImplementedError("the fused kernel implements DiceLoss(softmax=True, weight=None)")
-        return ops.dice_ce_loss(inputs, target, 1.0, 0.0)
+        if softmax and weight is None:
+            return ops.dice_ce_loss(inputs, target, 1.0, 0.0)
+        return ops.seg_loss(inputs, target, w_dice=1.0, dice_class_weights=weight, from_probs=not softmax)
 
 
 class BoundaryDoULoss(nn.Module):
@@ -35,13 +41,44 @@ class BoundaryDoULoss(nn.Module):
         return ops.dice_ce_loss(inputs, target, 0.0, 0.0, 1.0)
 
 
+class JaccardLoss(nn.Module):
+    """core.py:134-158: mean over the classes of 1 - (I + smooth) / (union + smooth) on the pixels whose label is not
+    ignore_index (`flatten`, utils/utils.py:39-50).  input [B,K,H,W] logits, target [B,H,W] class ids as floats."""
+
+    def __init__(self, ignore_index=255, smooth=1.0):
+        super().__init__()
+        self.ignore_index = ignore_index
+        self.smooth = smooth
+
+    def forward(self, input, target):
+        return ops.seg_loss(input, target, w_jaccard=1.0, ignore_index=self.ignore_index, jaccard_smooth=self.smooth)
+
+
+def _class_weights(value, K, name):
+    """None, a comma string or a sequence of K floats -> None or a list of K floats"""
+    if value is None:
+        return None
+    vals = [float(v) for v in (value.split(',') if isinstance(value, str) else value)]
+    if len(vals) != K:
+        raise ValueError(f"{name}: {len(vals)} weights for {K} classes")
+    return vals
+
+
 class Criterion(nn.Module):
+    """core.py:161-188 with `jaccard` as a fourth loss name and four optional attributes of `args` (each read with a default):
+    dice_class_weights / ce_class_weights (comma string or sequence of num_classes floats), ignore_index (int) and
+    jaccard_smooth (default 1.0).  Without any of them and without `jaccard` the call is ops.dice_ce_loss as before.
+    The class weights are uploaded at construction into the buffer `class_weights` ([2K]: Dice, then CE), which follows
+    .to(); writing new values into it takes effect at the next call, inside a captured graph too.
+    CE over a batch whose every pixel is ignored is NaN (as torch.nn.CrossEntropyLoss); boundary + ignore_index is refused."""
+
     def __init__(self, num_classes, args):
         super().__init__()
         self.num_classes = num_classes
         names = args.loss_type.split(',')
         weights = [float(w) for w in args.loss_weights.split(',')]
-        self.w_dice = self.w_ce = self.w_bd = 0.0
+        self.w_dice = self.w_ce = self.w_bd = self.w_jac = 0.0
+        has_jaccard = False
         for n, w in zip(names, weights):
             if n == "dice":
                 self.w_dice += w
@@ -49,8 +86,31 @@ class Criterion(nn.Module):
                 self.w_ce += w
             elif n == "boundary":
                 self.w_bd += w
+            elif n == "jaccard":
+                self.w_jac += w
+                has_jaccard = True
             else:
                 raise NotImplementedError(f"Loss {n} not implemented")
+        wd = _class_weights(getattr(args, "dice_class_weights", None), num_classes, "dice_class_weights")
+        wc = _class_weights(getattr(args, "ce_class_weights", None), num_classes, "ce_class_weights")
+        ignore_index = getattr(args, "ignore_index", None)
+        self.ignore_index = None if ignore_index is None else int(ignore_index)
+        smooth = getattr(args, "jaccard_smooth", None)
+        self.jaccard_smooth = 1.0 if smooth is None else float(smooth)
+        self.extended = has_jaccard or wd is not None or wc is not None or ignore_index is not None or smooth is not None
+        if self.ignore_index is not None and self.w_bd != 0.0:
+            raise NotImplementedError("Loss boundary with ignore_index not implemented: the reference defines no boundary count "
+                                      "over a label mask with holes")
+        if wd is not None or wc is not None:
+            ones = [1.0] * num_classes
+            self.register_buffer("class_weights", torch.tensor((wd or ones) + (wc or ones), dtype=torch.float32))
+        else:
+            self.class_weights = None
 
     def forward(self, outputs, labels):
-        return ops.dice_ce_loss(outputs, labels, self.w_dice, self.w_ce, self.w_bd)
+        if not self.extended:
+            return ops.dice_ce_loss(outputs, labels, self.w_dice, self.w_ce, self.w_bd)
+        K, cw = self.num_classes, self.class_weights
+        return ops.seg_loss(outputs, labels, w_dice=self.w_dice, w_ce=self.w_ce, w_boundary=self.w_bd, w_jaccard=self.w_jac,
+                            dice_class_weights=None if cw is None else cw[:K], ce_class_weights=None if cw is None else cw[K:],
+                            ignore_index=self.ignore_index, jaccard_smooth=self.jaccard_smooth)

@@ -99,4 +99,91 @@ def dice_ce_loss(logits, labels, w_dice=0.5, w_ce=0.5, w_boundary=0.0):
     return DiceCELossFn.apply(logits, labels, w_dice, w_ce, w_boundary)
 
 
+class SegLossExFn(Function):
+    """The loss with options (csrc/seg_loss_ex.hip): class weights, ignore_index, a Jaccard term, DiceLoss(softmax=False).
+    Forward = one pass that stores a row of partial sums per workgroup + a one-workgroup launch that adds the rows in a fixed
+    order (no float atomics: bitwise reproducible); backward = one launch.  cw: [2K] device weights (Dice, then CE) or None."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, cw, cfg):
+        logits, labels = _c(logits), _c(labels)
+        B, K, H, W = logits.shape
+        ws = _empty((kern.seg_loss_ex_ws_floats(B, K, H, W),), logits)
+        loss = _empty((1,), logits)
+        kern.seg_loss_ex_fwd(logits, labels, cw, ws, loss, B, K, H, W, *cfg)
+        ctx.save_for_backward(logits, labels, ws)
+        ctx.cw, ctx.cfg = cw, cfg
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, ws = ctx.saved_tensors
+        B, K, H, W = logits.shape
+        d = torch.empty_like(logits)
+        kern.seg_loss_ex_bwd(logits, labels, ctx.cw, ws, _c(g).reshape(1), d, B, K, H, W, *ctx.cfg)
+        return d, None, None, None
+
+
+_CLASS_WEIGHTS: dict = {}  # (device, K, Dice weights, CE weights) -> the [2K] device buffer uploaded for them
+
+
+def class_weight_buffer(K: int, dice_class_weights, ce_class_weights, device):
+    """The [2K] fp32 buffer (Dice weights, then CE weights) the loss kernels read, or None when both are None (all ones).
+    Sequences of K numbers are uploaded once per (device, values) and cached.  Device tensors are used as they are when they
+    are the two halves of one contiguous buffer (a later write into it is seen by the next launch, a graph replay included);
+    any other pair of tensors, or a tensor with a sequence / None, is packed by one device copy per call."""
+    wd, wc = dice_class_weights, ce_class_weights
+    if wd is None and wc is None:
+        return None
+    device = torch.device(device)
+    for name, w in (("dice_class_weights", wd), ("ce_class_weights", wc)):
+        if w is None:
+            continue
+        n = w.numel() if isinstance(w, Tensor) else len(w)
+        if n != K:
+            raise ValueError(f"{name}: {n} weights for {K} classes")
+        if isinstance(w, Tensor) and (w.dtype != torch.float32 or w.device != device):
+            raise ValueError(f"{name}: expected an fp32 tensor on {device}, got {w.dtype} on {w.device}")
+    if isinstance(wd, Tensor) or isinstance(wc, Tensor):
+        if (isinstance(wd, Tensor) and isinstance(wc, Tensor) and wd.is_contiguous() and wc.is_contiguous()
+                and wd.untyped_storage().data_ptr() == wc.untyped_storage().data_ptr()
+                and wc.storage_offset() == wd.storage_offset() + K):
+            return wd.detach().reshape(-1).as_strided((2 * K,), (1,), wd.storage_offset())
+        def half(w):
+            if isinstance(w, Tensor):
+                return w.detach().reshape(-1)
+            return class_weight_buffer(K, [1.0] * K if w is None else w, None, device)[:K]
+
+        return torch.cat([half(wd), half(wc)])
+    key = (str(device), K, None if wd is None else tuple(float(x) for x in wd), None if wc is None else tuple(float(x) for x in wc))
+    buf = _CLASS_WEIGHTS.get(key)
+    if buf is None:
+        ones = [1.0] * K
+        vals = list(key[2] if wd is not None else ones) + list(key[3] if wc is not None else ones)
+        buf = _CLASS_WEIGHTS[key] = torch.tensor(vals, dtype=torch.float32).to(device)
+    return buf
+
+
+def seg_loss(logits, labels, *, w_dice=0., w_ce=0., w_boundary=0., w_jaccard=0., dice_class_weights=None,
+             ce_class_weights=None, ignore_index=None, jaccard_smooth=1.0, from_probs=False):
+    """loss = w_dice Dice + w_ce CE + w_boundary BoundaryDoU + w_jaccard Jaccard on logits [B,K,H,W] (fp32 or bf16) and labels
+    [B,H,W] (class ids as floats, each in [0,K) or equal to ignore_index), sums over the whole batch (include/cenet_hip.h spells
+    the terms out).  dice_class_weights: DiceLoss.forward's `weight` (core.py:67-80); ce_class_weights / ignore_index:
+    torch.nn.CrossEntropyLoss(weight, ignore_index), mean reduction — a batch whose every pixel is ignored gives NaN, as torch
+    does; ignore_index also masks the Dice and Jaccard sums as `flatten` (utils/utils.py:39-50) does.  from_probs:
+    DiceLoss(softmax=False), the input holds probabilities and the gradient is with respect to them.  The gradient goes to
+    `logits` only and is exactly 0 at ignored pixels."""
+    if logits.dim() != 4 or labels.shape != (logits.shape[0],) + tuple(logits.shape[2:]):
+        raise ValueError(f"seg_loss: logits [B,K,H,W] and labels [B,H,W], got {tuple(logits.shape)} and {tuple(labels.shape)}")
+    if from_probs and (w_ce != 0 or w_boundary != 0 or w_jaccard != 0):
+        raise ValueError("seg_loss: from_probs is DiceLoss(softmax=False): only the Dice term is defined on probabilities")
+    if ignore_index is not None and w_boundary != 0:
+        raise NotImplementedError("seg_loss: BoundaryDoU with ignore_index (a boundary count over a mask with holes is not "
+                                  "defined by the reference)")
+    cw = class_weight_buffer(logits.shape[1], dice_class_weights, ce_class_weights, logits.device)
+    cfg = (float(w_dice), float(w_ce), float(w_boundary), float(w_jaccard), float(jaccard_smooth),
+           None if ignore_index is None else int(ignore_index), bool(from_probs))
+    return SegLossExFn.apply(logits, labels, cw, cfg)
+
+
 __all__ = [n for n in dir() if not n.startswith("__")]

@@ -35,12 +35,19 @@ def _as_batches(loader) -> Iterable[dict]:
     return loader
 
 
+def criterion_args(loss_type: str = "dice,ce", loss_weights: str = "0.5,0.5", dice_class_weights=None, ce_class_weights=None,
+                   ignore_index=None) -> argparse.Namespace:
+    """the `args` train_acdc hands losses.Criterion"""
+    return argparse.Namespace(loss_type=loss_type, loss_weights=loss_weights, dice_class_weights=dice_class_weights,
+                              ce_class_weights=ce_class_weights, ignore_index=ignore_index)
+
+
 def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, base_lr: float = 0.05, momentum: float = 0.9,
                weight_decay: float = 1e-4, loss_type: str = "dice,ce", loss_weights: str = "0.5,0.5", device="cuda:0",
                graph: bool = True, val_batches: Optional[Callable[[], Iterable]] = None, log_every: int = 20,
                log: Callable[[str], None] = print, optimizer: str = "sgd", scheduler: str = "poly",
                test_volumes: Optional[Callable[[], Iterable]] = None, save_dir: Optional[str] = None, img_size: int = 224,
-               test_resize: str = "device") -> dict:
+               test_resize: str = "device", dice_class_weights=None, ce_class_weights=None, ignore_index=None) -> dict:
     """main_acdc.py:200-290.  tr_loader yields {'image' [B,1,H,W] float, 'label' [B,H,W]} batches (host or device tensors);
     val_batches() yields (image [1,1,H,W], label [1,H,W]) pairs for the per-epoch validation (main_acdc.py:218-231).
     optimizer / scheduler: the reference's --optimizer / --scheduler strings (main_acdc.py:34-35, core.py:12-41); `momentum`
@@ -51,7 +58,9 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
     written (main_acdc.py:272-278: a validation gain without a test gain moves neither); the last epoch writes
     `epoch=<e>_lr=<lr>_avg_dcs=<last test dice>.pth` (:286-289).  Files go to save_dir (None: none are written).
     -> {'loss': per-iteration losses read back at log points, 'epoch_loss': [...], 'val_dice': [...], 'lr': [...]} and, with
-    test_volumes, 'test_dice' / 'test_hd95' (one entry per inference run) and 'best_epochs' (epochs that wrote best.pth)"""
+    test_volumes, 'test_dice' / 'test_hd95' (one entry per inference run) and 'best_epochs' (epochs that wrote best.pth)
+    loss_type may name `jaccard`; dice_class_weights / ce_class_weights (comma string or num_classes floats) and ignore_index
+    are losses.Criterion's optional attributes of the same names (None: the loss path without them)"""
     import os
 
     from . import checkpoint, evaluate
@@ -61,7 +70,8 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
         raise ValueError("save_dir: the checkpoints of main_acdc.py:272-289 are written by the test inference, pass test_volumes")
     dev = torch.device(device)
     net = net.to(dev).train()
-    crit = losses.Criterion(num_classes, argparse.Namespace(loss_type=loss_type, loss_weights=loss_weights))
+    crit = losses.Criterion(num_classes, criterion_args(loss_type, loss_weights, dice_class_weights, ce_class_weights,
+                                                        ignore_index)).to(dev)
     arena = optim.ParamArena(net, optim.cenet_segments())
     if optimizer.lower() == "sgd":
         opt = optim.FusedSGD(arena, lr=base_lr, momentum=momentum, weight_decay=weight_decay)

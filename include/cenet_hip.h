@@ -542,6 +542,27 @@ int cenet_seg_loss_fwd_f32(const float* logits, const float* labels, float* acc,
                            float w_dice, float w_ce, float w_bd, cenet_stream_t stream);
 int cenet_seg_loss_bwd_f32(const float* logits, const float* labels, const float* acc, const float* gout, float* dlogits,
                            int B, int K, int H, int W, float w_dice, float w_ce, float w_bd, cenet_stream_t stream);
+/* The loss with options (seg_loss_ex.hip): per-class weights, ignore_index, a Jaccard term (utils/core.py:134-158 with the
+ * `flatten` of utils/utils.py:39-50) and DiceLoss(softmax=False) (core.py:67-80).  With M = [label != ignore_index] (1 everywhere
+ * unless has_ignore), t_c = [label == c] M and sums over the whole batch, I_c = sum M p_c t_c, Z_c = sum M p_c^2, Y_c = sum t_c,
+ * S_c = sum M p_c:
+ *   loss = w_dice/K sum_c wd_c (1 - (2 I_c + 1e-5) / (Z_c + Y_c + 1e-5))  +  w_ce sum_pix wc_t (-log p_t) / sum_pix wc_t
+ *        + w_bd BoundaryDoU  +  w_jac/K sum_c (1 - (I_c + smooth) / (S_c + Y_c - I_c + smooth)).
+ * A term whose weight is 0 is left out (not multiplied by 0): the CE of a batch whose every pixel is ignored is NaN, as torch's.
+ * cw: [2K] floats, the Dice class weights wd then the CE class weights wc, read on the device by every launch (NULL: all ones).
+ * Labels are in [0,K) or equal ignore_index.  from_probs: `logits` already holds the probabilities (no softmax either way);
+ * Dice term only, anything else returns 1.  has_ignore with w_bd != 0 returns 2 (a boundary count over a mask with holes is
+ * not defined by the reference).  The gradient of an ignored pixel is exactly 0.
+ * ws: workspace of ws_floats >= cenet_seg_loss_ex_ws_floats(B, K, H, W) floats, else 1 is returned.  No float atomics: each
+ * workgroup of the forward stores one row of partial sums, a one-workgroup second launch adds the rows in a fixed order and
+ * leaves the compact sums at the head of ws for the backward call — bitwise reproducible.  K <= 16, B <= 65535. */
+long cenet_seg_loss_ex_ws_floats(int B, int K, int H, int W);
+int cenet_seg_loss_ex_fwd_f32(const float* logits, const float* labels, const float* cw, float* ws, long ws_floats, float* loss,
+                              int B, int K, int H, int W, float w_dice, float w_ce, float w_bd, float w_jac, float smooth,
+                              int has_ignore, int ignore_index, int from_probs, cenet_stream_t stream);
+int cenet_seg_loss_ex_bwd_f32(const float* logits, const float* labels, const float* cw, const float* ws, const float* gout,
+                              float* dlogits, int B, int K, int H, int W, float w_dice, float w_ce, float w_bd, float w_jac,
+                              float smooth, int has_ignore, int ignore_index, int from_probs, cenet_stream_t stream);
 /* Evaluation (main_acdc.py:218-231 val(), metrics_eval.py:24-34,46-49): pred[B,HW] = argmax over the K
  * logit planes (class ids as floats, may be NULL), counts[(K+1)*3] (uint32, zero-filled by the call; may be NULL together with
  * labels) = per class {|pred==c & gt==c|, |pred==c|, |gt==c|} and, in row K, the same for the binary masks pred>0 / gt>0. */
@@ -675,6 +696,13 @@ int cenet_seg_loss_bwd_bf16(const unsigned short* logits, const float* labels, c
     short* dlogits, int B, int K, int H, int W, float w_dice, float w_ce, float w_bd, cenet_stream_t stream);
 int cenet_argmax_counts_bf16(const unsigned short* logits, const float* labels, float* pred, unsigned* counts, int B, int K,
     int HW, cenet_stream_t stream);
+/* seg_loss_ex.hip */
+int cenet_seg_loss_ex_fwd_bf16(const unsigned short* logits, const float* labels, const float* cw, float* ws, long ws_floats,
+    float* loss, int B, int K, int H, int W, float w_dice, float w_ce, float w_bd, float w_jac, float smooth, int has_ignore,
+    int ignore_index, int from_probs, cenet_stream_t stream);
+int cenet_seg_loss_ex_bwd_bf16(const unsigned short* logits, const float* labels, const float* cw, const float* ws, const float*
+    gout, unsigned short* dlogits, int B, int K, int H, int W, float w_dice, float w_ce, float w_bd, float w_jac, float smooth,
+    int has_ignore, int ignore_index, int from_probs, cenet_stream_t stream);
 /* norm.hip */
 int cenet_layernorm_fwd_bf16(const unsigned short* x, const float* gamma, const float* beta, unsigned short* y, float* mean,
     float* rstd, int rows, int C, float eps, cenet_stream_t stream);
