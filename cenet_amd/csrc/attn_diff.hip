@@ -25,7 +25,17 @@
 //     (24 significant bits) per (head, query), and one extra k-step against a constant -1 fragment gives S - lse/scale and
 //     dP - delta straight out of the MFMA;
 //   * base-2 exponentials with scale*log2(e) folded into one multiply per score; the running maximum of the forward pass is
-//     rescaled only when some lane of the wave actually raised it (wave-uniform branch).
+//     rescaled only when some lane of the wave actually raised it (wave-uniform branch);
+//   * the key loops of the forward and dQ kernels hold ONE instantiation of the tile body, the unmasked one, and run over the
+//     full 32-key tiles; the masked instantiation runs once after the loop on the ragged last tile (N % 32 keys), which the
+//     fetch -> stage -> barrier pipeline delivers like any other tile.  The trip count depends on N alone, so every wave of a
+//     workgroup meets the same barriers whatever its q0.  With both instantiations inside the loop (`klim < 32 ? masked :
+//     unmasked` per iteration) the register allocator gave the two bodies' results different registers and copied every
+//     loop-carried accumulator across the join: 32-36 v_mov_b64 / v_mov_b32 per iteration and 30-70 more registers per instance
+//     (hd 16: forward 168 -> 122, Non-local forward 194 -> 129; profiles/r07_attn_isa.md);
+//   * the softmax denominator stays on the VALU (one v_add_f32 per score): accumulating it on the matrix pipe against an
+//     all-ones A fragment costs 16 registers per head, which takes the hd-16 forward from four waves per SIMD back to three
+//     and measured 7 % SLOWER.
 #include "common.h"
 #include "../../include/cenet_hip.h"
 #include <cstdlib>
@@ -177,8 +187,14 @@ struct DaGeo {
 // ONE: a single softmax over BOTH halves of the pair's 2*HDP query / key columns (one head of dimension 2*HDP = value width):
 // plain attention with head dimension 64 through the same tiles — the two half-products add into one score tile.  Tensors:
 // q, k, v [B, N, H*2HDP], U [B, H, N, 2HDP], lse / aug rows [B, H, N].
+// Workgroups per CU the registers of an instance are bounded for: MINB, except for the single-softmax instance at HDP = 32.  That
+// one takes 129 registers with one tile body in the key loop; bounded to FOUR workgroups it takes 127, nothing spilled (17.6 KB of
+// LDS fit four times): 0.203 -> 0.181 ms through ops.nonlocal_attention at 56x56, batch 32, same box.  The instance keeps the
+// template arguments <32, 1, 2, true> — its symbol is the key of the committed profiles — so the `2` written at its launch site
+// (cenet_attn64_fwd_bf16) is NOT its bound; a static_assert there says so.
+constexpr int da_fwd_wg_per_cu(int hdp, int minb, bool one) { return (one && hdp == 32) ? 4 : minb; }
 template <int HDP, int QT, int MINB, bool ONE, bool H4 = false>
-__global__ __launch_bounds__(256, MINB) void dattn_fwd_kernel(DiffArgs a) {
+__global__ __launch_bounds__(256, da_fwd_wg_per_cu(HDP, MINB, ONE)) void dattn_fwd_kernel(DiffArgs a) {
   typedef DaGeo<HDP> G;
   constexpr int NKS = HDP / 16, NDT = G::DVP / 32, NH = ONE ? 1 : 2;
   constexpr int KIMG = 32 * G::KP, VIMG = 32 * G::VPT + 64, IMG = KIMG + VIMG;  // (+64: transposed reads of padded rows)
@@ -255,88 +271,90 @@ __global__ __launch_bounds__(256, MINB) void dattn_fwd_kernel(DiffArgs a) {
       l[t][s] = 0.f;
     }
   }
+  // One score-tile body for the key loop: `masked` selects the instantiation.  The loop below holds ONLY the unmasked one (full
+  // 32-key tiles); the masked one runs once, after the loop, on the ragged last tile.  (With both instantiations inside the loop
+  // the register allocator gave their accumulators different registers and copied O / dQ across the join on every iteration.)
+  auto tile = [&](auto masked, const bf* Kimg, const bf* Vimg, int klim) __attribute__((always_inline)) {
+    constexpr bool MASKED = decltype(masked)::value;
+    // HDP <= 32: the tile's K / V fragments are read once and shared by both heads (and all QT query tiles).  HDP = 64 has
+    // 128 accumulator registers per wave: fragments are read where they are used (LATE) — holding them across the softmax
+    // cost 640 bytes of scratch per lane when the key loop still held two tile bodies (256 + 256 registers and 400 B of scratch
+    // even with LATE; one body: 254 + 148, no scratch, HDP = 48: 208 + 112).  Whether LATE is still needed was not re-measured.
+    constexpr bool LATE = HDP > 32;
+    bf16x8 kf[LATE ? 1 : 2][NKS], vf[LATE ? 1 : NDT][2];
+    if (!LATE) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) kf[LATE ? 0 : s][ks] = da_rm(Kimg, G::KP, r, s * HDP + 16 * ks, hh);
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) vf[LATE ? 0 : dt][s2] = da_tr(Vimg, G::VPT, s2, 32 * dt, lane);
+    }
+#pragma unroll
+    for (int t = 0; t < QT; ++t)
+#pragma unroll
+      for (int s = 0; s < NH; ++s) {
+        f32x16 S = da_zero();
+#pragma unroll
+        for (int sp = (ONE ? 0 : s); sp <= (ONE ? 1 : s); ++sp)
+#pragma unroll
+          for (int ks = 0; ks < NKS; ++ks)
+            S = DA_MFMA(LATE ? da_rm(Kimg, G::KP, r, sp * HDP + 16 * ks, hh) : kf[LATE ? 0 : sp][ks], qf[t][sp][ks], S);  // S^T[key][query]
+        if (MASKED) {  // ragged last tile only (its own instantiation of the tile body: no per-score selects elsewhere)
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (da_row(i, hh) >= klim) S[i] = DA_NEG;
+        }
+        float mx = da_max3(S[0], S[1], S[2]);
+#pragma unroll
+        for (int i = 3; i < 15; i += 2) mx = da_max3(mx, S[i], S[i + 1]);
+        mx = fmaxf(mx, S[15]);
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        if (da_any(mx > m[t][s])) {  // some query of the wave raised its maximum: rescale (wave-uniform branch)
+          const float mn = fmaxf(m[t][s], mx);
+          const float alpha = da_exp2((m[t][s] - mn) * c);
+          m[t][s] = mn;
+          l[t][s] *= alpha;
+#pragma unroll
+          for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) O[t][s][dt][i] *= alpha;
+        }
+        const float mc = m[t][s] * c;
+        float rs = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const float p = da_exp2(S[i] * c - mc);
+          S[i] = p;
+          rs += p;
+        }
+        l[t][s] += rs;
+        const bf16x8 p0 = da_pack8(S, 0), p1 = da_pack8(S, 1);
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) {  // O^T[value feature][query] += V^T[feature][key] P^T[key][query]
+          O[t][s][dt] = DA_MFMA(LATE ? da_tr(Vimg, G::VPT, 0, 32 * dt, lane) : vf[LATE ? 0 : dt][0], p0, O[t][s][dt]);
+          O[t][s][dt] = DA_MFMA(LATE ? da_tr(Vimg, G::VPT, 1, 32 * dt, lane) : vf[LATE ? 0 : dt][1], p1, O[t][s][dt]);
+        }
+      }
+  };
+  const int nfull = N & ~31;  // keys in full tiles; the same for every wave: equal barrier counts whatever q0
   fetch(0);
   stage(0);
   __syncthreads();
   int cur = 0;
-  for (int k0 = 0; k0 < N; k0 += 32) {
-    const bool more = k0 + 32 < N;
+  for (int k0 = 0; k0 < nfull; k0 += 32) {
+    const bool more = k0 + 32 < N;  // (the ragged tile is fetched and staged like any other)
     if (more) fetch(k0 + 32);
-    const bf* Kimg = lds + cur * IMG;
-    const bf* Vimg = Kimg + KIMG;
-    const int klim = N - k0;  // valid keys of this tile (>= 32 except in the last one)
-    auto tile = [&](auto masked) __attribute__((always_inline)) {
-      constexpr bool MASKED = decltype(masked)::value;
-      // HDP <= 32: the tile's K / V fragments are read once and shared by both heads (and all QT query tiles).  HDP = 64 has
-      // 128 accumulator registers per wave: fragments are read where they are used (LATE) — holding them across the softmax
-      // cost 640 bytes of scratch per lane.
-      constexpr bool LATE = HDP > 32;
-      bf16x8 kf[LATE ? 1 : 2][NKS], vf[LATE ? 1 : NDT][2];
-      if (!LATE) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int ks = 0; ks < NKS; ++ks) kf[LATE ? 0 : s][ks] = da_rm(Kimg, G::KP, r, s * HDP + 16 * ks, hh);
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) vf[LATE ? 0 : dt][s2] = da_tr(Vimg, G::VPT, s2, 32 * dt, lane);
-      }
-#pragma unroll
-      for (int t = 0; t < QT; ++t)
-#pragma unroll
-        for (int s = 0; s < NH; ++s) {
-          f32x16 S = da_zero();
-#pragma unroll
-          for (int sp = (ONE ? 0 : s); sp <= (ONE ? 1 : s); ++sp)
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks)
-              S = DA_MFMA(LATE ? da_rm(Kimg, G::KP, r, sp * HDP + 16 * ks, hh) : kf[LATE ? 0 : sp][ks], qf[t][sp][ks], S);  // S^T[key][query]
-          if (MASKED) {  // ragged last tile only (its own instantiation of the tile body: no per-score selects elsewhere)
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-              if (da_row(i, hh) >= klim) S[i] = DA_NEG;
-          }
-          float mx = da_max3(S[0], S[1], S[2]);
-#pragma unroll
-          for (int i = 3; i < 15; i += 2) mx = da_max3(mx, S[i], S[i + 1]);
-          mx = fmaxf(mx, S[15]);
-          mx = fmaxf(mx, __shfl_xor(mx, 32));
-          if (da_any(mx > m[t][s])) {  // some query of the wave raised its maximum: rescale (wave-uniform branch)
-            const float mn = fmaxf(m[t][s], mx);
-            const float alpha = da_exp2((m[t][s] - mn) * c);
-            m[t][s] = mn;
-            l[t][s] *= alpha;
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-              for (int i = 0; i < 16; ++i) O[t][s][dt][i] *= alpha;
-          }
-          const float mc = m[t][s] * c;
-          float rs = 0.f;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const float p = da_exp2(S[i] * c - mc);
-            S[i] = p;
-            rs += p;
-          }
-          l[t][s] += rs;
-          const bf16x8 p0 = da_pack8(S, 0), p1 = da_pack8(S, 1);
-#pragma unroll
-          for (int dt = 0; dt < NDT; ++dt) {  // O^T[value feature][query] += V^T[feature][key] P^T[key][query]
-            O[t][s][dt] = DA_MFMA(LATE ? da_tr(Vimg, G::VPT, 0, 32 * dt, lane) : vf[LATE ? 0 : dt][0], p0, O[t][s][dt]);
-            O[t][s][dt] = DA_MFMA(LATE ? da_tr(Vimg, G::VPT, 1, 32 * dt, lane) : vf[LATE ? 0 : dt][1], p1, O[t][s][dt]);
-          }
-        }
-    };
-    if (q0 < N) {  // wave-uniform: a wave past the last query only helps with the staging
-      if (klim < 32) tile(da_true());
-      else tile(da_false());
-    }
+    // (wave-uniform: a wave past the last query only helps with the staging)
+    if (q0 < N) tile(da_false(), lds + cur * IMG, lds + cur * IMG + KIMG, 32);
     if (more) stage(cur ^ 1);
     __syncthreads();
     cur ^= 1;
   }
+  // ragged last tile (N % 32 keys): staged by the last loop iteration (by the prologue when N < 32), nothing is staged after it
+  if (nfull < N && q0 < N) tile(da_true(), lds + cur * IMG, lds + cur * IMG + KIMG, N - nfull);
   if (q0 >= N) return;
 #pragma unroll
   for (int t = 0; t < QT; ++t) {
@@ -369,8 +387,10 @@ __global__ __launch_bounds__(256, MINB) void dattn_fwd_kernel(DiffArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------------
 // backward, dQ (+ delta = rowsum(dU * U) and the bf16 statistics rows for dK/dV): wave = 32 queries x both softmax heads
 // ---------------------------------------------------------------------------------------------------------------------------
-// (HDP <= 16: three workgroups per CU — 168 registers, nothing spilled; the kernel waits on dependent MFMA / exponential chains, a
-// third wave per SIMD covers more of them: 0.78 -> 0.74 ms at DSEB-56x56, same box)
+// (HDP <= 16: three workgroups per CU — 167 registers under the 168 cap, nothing spilled (H4: 140); the kernel waits on dependent
+// MFMA / exponential chains, a third wave per SIMD covers more of them: 0.78 -> 0.74 ms at DSEB-56x56, same box.  Bounded to four
+// workgroups it takes 128 registers and 20 B of scratch and measures 1.394 - 1.403 against 1.402 - 1.420 ms for the whole backward:
+// inside the spread, not taken.)
 template <int HDP, bool ONE, bool H4 = false>
 __global__ __launch_bounds__(256, HDP > 32 ? 1 : (HDP <= 16 ? 3 : 2)) void dattn_bwd_dq_kernel(DiffArgs a) {
   typedef DaGeo<HDP> G;
@@ -463,63 +483,63 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : (HDP <= 16 ? 3 : 2)) void dattn
       memcpy(a.aug + hrow * 16 + 8 * hh, row8, 16);
     }
   }
+  // one tile body; the key loop holds only its unmasked instantiation, the ragged last tile runs once after it (see the forward)
+  auto tile = [&](auto masked, const bf* Kimg, const bf* Vimg, int klim) __attribute__((always_inline)) {
+    constexpr bool MASKED = decltype(masked)::value;
+    bf16x8 vf[NKD];
+#pragma unroll
+    for (int kd = 0; kd < NKD; ++kd) vf[kd] = da_rm(Vimg, G::VPR, r, 16 * kd, hh);
+#pragma unroll
+    for (int s = 0; s < NH; ++s) {
+      // the query is the MFMA column: its delta is a lane constant, so the dP chain can start from -delta (dP - delta comes out
+      // of the accumulator: one VALU instruction per score less).  Not at HDP = 16: a zero accumulator is an inline constant of
+      // the first MFMA, a -delta one is 16 live registers more, and that instance sat on its 168-register cap (30 spilled) while
+      // the key loop held two tile bodies.  With one body it fits (165 registers, no scratch) but trades the 30 packed ops of the
+      // step for scalar ones, 123 -> 121 vector instructions: 1.370 - 1.416 against 1.417 - 1.425 ms for the DSEB-56x56 backward, same
+      // box — inside the spread, left as it is.
+      constexpr bool INITD = HDP > 16;
+      f32x16 S = da_zero(), dP;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) dP[i] = INITD ? -dl[s] : 0.f;
+#pragma unroll
+      for (int sp = (ONE ? 0 : s); sp <= (ONE ? 1 : s); ++sp)
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) S = DA_MFMA(da_rm(Kimg, G::KP, r, sp * HDP + 16 * ks, hh), qf[sp][ks], S);
+#pragma unroll
+      for (int kd = 0; kd < NKD; ++kd) dP = DA_MFMA(vf[kd], gf[s][kd], dP);  // dP^T[key][query] = V dU^T - delta
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        float p = da_exp2(S[i] * c - lse2[s]);
+        if (MASKED && da_row(i, hh) >= klim) p = 0.f;
+        S[i] = INITD ? p * dP[i] : p * (dP[i] - dl[s]);
+      }
+      // dQ^T[d][query] += K^T[d][key] dS^T[key][query]; accumulator rows >= hd (the other head's columns, padding) are
+      // never stored
+#pragma unroll
+      for (int sp = (ONE ? 0 : s); sp <= (ONE ? 1 : s); ++sp)
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          const bf16x8 dsB = da_pack8(S, s2);
+#pragma unroll
+          for (int ft = 0; ft < NFT; ++ft)
+            dq[sp][ft] = DA_MFMA(da_tr(Kimg, G::KP, s2, sp * HDP + 32 * ft, lane), dsB, dq[sp][ft]);
+        }
+    }
+  };
+  const int nfull = N & ~31;
   fetch(0);
   stage(0);
   __syncthreads();
   int cur = 0;
-  for (int k0 = 0; k0 < N; k0 += 32) {
+  for (int k0 = 0; k0 < nfull; k0 += 32) {
     const bool more = k0 + 32 < N;
     if (more) fetch(k0 + 32);
-    const bf* Kimg = lds + cur * IMG;
-    const bf* Vimg = Kimg + KIMG;
-    const int klim = N - k0;
-    auto tile = [&](auto masked) __attribute__((always_inline)) {
-      constexpr bool MASKED = decltype(masked)::value;
-      bf16x8 vf[NKD];
-#pragma unroll
-      for (int kd = 0; kd < NKD; ++kd) vf[kd] = da_rm(Vimg, G::VPR, r, 16 * kd, hh);
-#pragma unroll
-      for (int s = 0; s < NH; ++s) {
-        // the query is the MFMA column: its delta is a lane constant, so the dP chain can start from -delta (dP - delta comes out
-        // of the accumulator: one VALU instruction per score less).  Not at HDP = 16: a zero accumulator is an inline constant of
-        // the first MFMA, a -delta one is 16 live registers more, and that instance sits on its 168-register cap (30 spilled).
-        constexpr bool INITD = HDP > 16;
-        f32x16 S = da_zero(), dP;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) dP[i] = INITD ? -dl[s] : 0.f;
-#pragma unroll
-        for (int sp = (ONE ? 0 : s); sp <= (ONE ? 1 : s); ++sp)
-#pragma unroll
-          for (int ks = 0; ks < NKS; ++ks) S = DA_MFMA(da_rm(Kimg, G::KP, r, sp * HDP + 16 * ks, hh), qf[sp][ks], S);
-#pragma unroll
-        for (int kd = 0; kd < NKD; ++kd) dP = DA_MFMA(vf[kd], gf[s][kd], dP);  // dP^T[key][query] = V dU^T - delta
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          float p = da_exp2(S[i] * c - lse2[s]);
-          if (MASKED && da_row(i, hh) >= klim) p = 0.f;
-          S[i] = INITD ? p * dP[i] : p * (dP[i] - dl[s]);
-        }
-        // dQ^T[d][query] += K^T[d][key] dS^T[key][query]; accumulator rows >= hd (the other head's columns, padding) are
-        // never stored
-#pragma unroll
-        for (int sp = (ONE ? 0 : s); sp <= (ONE ? 1 : s); ++sp)
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) {
-            const bf16x8 dsB = da_pack8(S, s2);
-#pragma unroll
-            for (int ft = 0; ft < NFT; ++ft)
-              dq[sp][ft] = DA_MFMA(da_tr(Kimg, G::KP, s2, sp * HDP + 32 * ft, lane), dsB, dq[sp][ft]);
-          }
-      }
-    };
-    if (q0 < N) {
-      if (klim < 32) tile(da_true());
-      else tile(da_false());
-    }
+    if (q0 < N) tile(da_false(), lds + cur * IMG, lds + cur * IMG + KIMG, 32);
     if (more) stage(cur ^ 1);
     __syncthreads();
     cur ^= 1;
   }
+  if (nfull < N && q0 < N) tile(da_true(), lds + cur * IMG, lds + cur * IMG + KIMG, N - nfull);
   if (q0 + r < N) {
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -656,11 +676,14 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : 2) void dattn_bwd_dkv_kernel(Di
 #pragma unroll
         for (int kd = 0; kd < NKD; ++kd) dP = DA_MFMA(da_rm(Gimg, G::VPR, r, 16 * kd, hh), vfB[kd], dP);  // dP[q][key] = dU V^T
         // row (query) statistics through the contraction: S -= lse / scale, dP -= delta
-        bf16x8 al = {0, 0, 0, 0, 0, 0, 0, 0}, ad = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (hh == 0) {
-          memcpy(&al, Aimg + r * AP + s * 16, 16);
-          memcpy(&ad, Aimg + r * AP + s * 16 + 8, 16);
-        }
+        // both lane halves read the row: the upper half's k = 8..15 meets the zero rows of negB, so its products are exact zeros
+        // and the result is bit-identical to loading the lower half only — for FINITE statistics, which is every staged term of a
+        // finite problem (three bf16 terms + five zeros per row from the dQ kernel, the finite fill 0x7149 beyond N).  A non-finite
+        // lse or delta (non-finite inputs only) now meets 0 in the upper half too: inf * 0 = NaN for that query's row, where the
+        // lower-half load kept it to the terms it touches.  No zero-filled fragments (16 v_mov_b32), no divergent branch per head.
+        bf16x8 al, ad;
+        memcpy(&al, Aimg + r * AP + s * 16, 16);
+        memcpy(&ad, Aimg + r * AP + s * 16 + 8, 16);
         S = DA_MFMA(al, negB, S);
         dP = DA_MFMA(ad, negB, dP);
 #pragma unroll
@@ -759,7 +782,8 @@ extern "C" int cenet_diffattn_heads_fwd_bf16(const cenet_diffattn_t* p, hipStrea
   if (a.hd == 4) {
     CENET_LAUNCH((dattn_fwd_kernel<16, 1, 3, false, true>), dim3(cdiv(a.N, 128), bh), dim3(256), stream, a);
   } else if (a.hd <= 16) {
-    // one 32-query tile per wave at three workgroups per CU (two tiles per wave need 256 registers and still spill)
+    // one 32-query tile per wave; bounded to three workgroups per CU, the kernel takes 122 registers and runs four (two tiles
+    // per wave: 198 registers, two workgroups)
     static const int v = getenv("CENET_DATTN_QT2") ? 2 : 1;
     if (v == 2 && a.N >= 1024) CENET_LAUNCH((dattn_fwd_kernel<16, 2, 2, false>), dim3(cdiv(a.N, 256), bh), dim3(256), stream, a);
     else CENET_LAUNCH((dattn_fwd_kernel<16, 1, 3, false>), dim3(cdiv(a.N, 128), bh), dim3(256), stream, a);
@@ -824,6 +848,8 @@ extern "C" int cenet_attn64_fwd_bf16(const cenet_diffattn_t* p, hipStream_t stre
   DiffArgs a;
   const int rc = da_fill64(a, p);
   if (rc != CENET_OK) return rc;
+  // <32, 1, 2, true> is bounded to four workgroups per CU, not to the two of its MINB argument (da_fwd_wg_per_cu)
+  static_assert(da_fwd_wg_per_cu(32, 2, true) == 4, "the single-softmax HDP = 32 forward is built for four workgroups per CU");
   if (a.hd == 32) CENET_LAUNCH((dattn_fwd_kernel<32, 1, 2, true>), dim3(cdiv(a.N, 128), a.B * a.H), dim3(256), stream, a);
   else CENET_LAUNCH((dattn_fwd_kernel<64, 1, 1, true>), dim3(cdiv(a.N, 128), a.B * a.H), dim3(256), stream, a);
   CENET_CHECK_LAUNCH();
