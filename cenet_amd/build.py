@@ -9,6 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcenet_hip.so")
+STAMPS_LIB = os.path.join(HERE, "libcenet_hip_stamps.so")
 
 
 # per-file flags: the attention kernels never produce or consume NaNs on purpose (masked scores are -1e30), and without
@@ -40,21 +41,28 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_hip(force: bool = False, verbose: bool = True) -> str:
-    """hipcc --offload-arch=gfx950 -> cenet_amd/libcenet_hip.so (cross-compiles without a GPU)."""
+def build_hip(force: bool = False, verbose: bool = True, stamps: bool = False, tr_builtin: bool = False) -> str:
+    """hipcc --offload-arch=gfx950 -> cenet_amd/libcenet_hip.so (cross-compiles without a GPU).
+    stamps: the diagnostic build of the ring GEMM with in-kernel clock reads (-DCENET_RING_STAMPS, csrc/gemm_ring.h) ->
+    cenet_amd/libcenet_hip_stamps.so, which only tools/ring_stamps.py loads; the product library is never built with it.
+    tr_builtin (with stamps): the K loops read row-fast fragments with the compiler's builtin again (-DCENET_RING_TR_BUILTIN), which
+    drains the ring every K-step: the loop as it was before round 8 -> cenet_amd/libcenet_hip_stamps_trb.so."""
+    diag = ([] if not stamps else ["-DCENET_RING_STAMPS"] + (["-DCENET_RING_TR_BUILTIN"] if tr_builtin else []))
+    LIB = (STAMPS_LIB.replace(".so", "_trb.so") if tr_builtin else STAMPS_LIB) if stamps else globals()["LIB"]
+    objdir = os.path.join(HERE, "csrc", ("obj_stamps_trb" if tr_builtin else "obj_stamps") if stamps else "obj")
     deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "cenet_hip.h")]
     if not force and not _stale(LIB, deps):
         return LIB
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objs = []
     procs = []
-    os.makedirs(os.path.join(HERE, "csrc", "obj"), exist_ok=True)
+    os.makedirs(objdir, exist_ok=True)
     for src in sources():
-        obj = os.path.join(HERE, "csrc", "obj", os.path.basename(src) + ".o")
+        obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
         if force or _stale(obj, [src] + deps[len(sources()):]):
             cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", src, "-o", obj,
-                   "-Wno-unused-result"] + EXTRA_FLAGS.get(os.path.basename(src), [])
+                   "-Wno-unused-result"] + EXTRA_FLAGS.get(os.path.basename(src), []) + diag
             if verbose:
                 print(" ".join(cmd), flush=True)
             procs.append((src, subprocess.Popen(cmd)))
@@ -69,5 +77,5 @@ def build_hip(force: bool = False, verbose: bool = True) -> str:
 
 
 if __name__ == "__main__":
-    build_hip(force="--force" in sys.argv)
-    print(LIB)
+    print(build_hip(force="--force" in sys.argv, stamps="--stamps" in sys.argv or "--stamps-tr-builtin" in sys.argv,
+                    tr_builtin="--stamps-tr-builtin" in sys.argv))

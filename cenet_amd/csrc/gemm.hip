@@ -27,6 +27,19 @@ static thread_local char g_last_kernel[96] = "";
 extern "C" const char* cenet_gemm_last_kernel(void) { return g_last_kernel; }
 static inline const char* tf(bool b) { return b ? "true" : "false"; }
 
+#ifdef CENET_RING_STAMPS
+// diagnostic build (gemm_ring.h, RingClock): the ring kernels launched after this call leave the per-segment cycle sums of
+// wave 0 of `n` evenly spaced workgroups in buf (16 words per workgroup); buf = null turns the stores off again
+static unsigned long long* g_stamp_buf = nullptr;
+static int g_stamp_n = 0;
+extern "C" int cenet_ring_stamps(unsigned long long* buf, int n) {
+  if (buf != nullptr && n <= 0) return CENET_EINVAL;
+  g_stamp_buf = buf;
+  g_stamp_n = buf ? n : 0;
+  return CENET_OK;
+}
+#endif
+
 // asum fallback for contractions the ring kernel does not take: asum[m] += sum over (kb, k) of A[kb*skb + m*sr + k*sc]
 template <typename GT>
 __global__ __launch_bounds__(256) void gemm_asum_kernel(const GT* __restrict__ A, long sr, long sc, long skb, int M, int K, int nkb,
@@ -144,6 +157,10 @@ static int gemm_dispatch(const cenet_mat_t* A, const cenet_mat_t* B, const cenet
   int akf = -1, bkf = -1;
   g.ring_unal = 0;
   g.a_end = g.b_end = nullptr;
+#ifdef CENET_RING_STAMPS
+  g.stamps = g_stamp_buf;
+  g.stamp_n = g_stamp_n;
+#endif
   if (bf && B->mode == 0 && A->kinner == 0 && B->kinner == 0) {
     auto e8 = [](long v) { return (v & 7) == 0; };
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };

@@ -41,6 +41,11 @@ struct GemmArgs {
   // next row; a_end / b_end = one past the last element of the operand (a chunk that would cross it is fetched by hand)
   int ring_unal;
   const void *a_end, *b_end;
+#ifdef CENET_RING_STAMPS
+  // diagnostic build only (gemm_ring.h, RingClock): per-segment cycle sums of wave 0 of stamp_n workgroups, 16 words each
+  unsigned long long* stamps;
+  int stamp_n;
+#endif
 };
 
 __device__ __forceinline__ unsigned f2bf_bits(float f) { return cenet_f2bf(f); }

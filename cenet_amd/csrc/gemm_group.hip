@@ -180,10 +180,14 @@ __global__ __launch_bounds__(256, (NS * (BM + BN) * 128 <= 80 * 1024 ? 2 : 1)) v
       bf16x8 a[MI], b[NJ];
 #pragma unroll
       for (int i = 0; i < MI; ++i)
-        a[i] = AKF ? ring_frag_kf(Ai, wm * (BM / 2) + i * 16, kc, lane) : ring_frag_rf<BM>(Ai, wm * (BM / 2) + i * 16, kc, lane);
+        a[i] = AKF ? ring_frag_kf(Ai, wm * (BM / 2) + i * 16, kc, lane) : ring_frag_rf_inflight<BM>(Ai, wm * (BM / 2) + i * 16, kc, lane);
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
-        b[j] = BKF ? ring_frag_kf(Bi, wn * (BN / 2) + j * 16, kc, lane) : ring_frag_rf<BN>(Bi, wn * (BN / 2) + j * 16, kc, lane);
+        b[j] = BKF ? ring_frag_kf(Bi, wn * (BN / 2) + j * 16, kc, lane) : ring_frag_rf_inflight<BN>(Bi, wn * (BN / 2) + j * 16, kc, lane);
+#pragma unroll
+      for (int i = 0; i < MI; ++i) ring_frag_landed<AKF>(a[i]);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) ring_frag_landed<BKF>(b[j]);
       if (klim_t < 64) {
         if (AKF) {
 #pragma unroll

@@ -64,6 +64,42 @@ __device__ __forceinline__ bf16x8 ring_frag_rf(const unsigned char* img, int r0,
   return f;
 }
 
+// The same fragment for a loop that keeps LDS-DMA tiles in flight across its reads (the ring K loops).  hipcc orders the builtin
+// form of the transposing read behind EVERY pending LDS-DMA: s_waitcnt vmcnt(0) in front of the first one of a K-step, which
+// drains the ring each step, so that a K-step lasts one whole DMA latency whatever the ring depth.  The ring's own counted vmcnt
+// and barrier already cover the tile read here, so the read is issued from inline asm, which the compiler does not order.  It
+// does not see the pending LDS return either: ring_frag_landed() goes between these reads and the first use of the fragment.
+template <int BX>
+__device__ __forceinline__ bf16x8 ring_frag_rf_inflight(const unsigned char* img, int r0, int kc, int lane) {
+#if defined(CENET_HOSTSIM_BUILD) || defined(CENET_RING_TR_BUILTIN)  // (the second: a diagnostic build that shows the drain)
+  return ring_frag_rf<BX>(img, r0, kc, lane);
+#else
+  constexpr int CH = BX / 8;
+  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
+  const int x = r0 + 4 * p;
+  bf16x8 f;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int k = kc * 32 + 8 * g + 4 * h + q;
+    const unsigned char* a = img + (k * CH + ((x >> 3) ^ rf_key<BX>(k))) * 16 + (x & 7) * 2;
+    ring_s4 v;
+    asm volatile("ds_read_b64_tr_b16 %0, %1"
+                 : "=v"(v)
+                 : "v"((unsigned)(__UINTPTR_TYPE__)(const __attribute__((address_space(3))) unsigned char*)a));
+    f[4 * h + 0] = v[0], f[4 * h + 1] = v[1], f[4 * h + 2] = v[2], f[4 * h + 3] = v[3];
+  }
+  return f;
+#endif
+}
+// after the fragment reads of a step and before their first use: the row-fast fragments' reads (inline asm) have returned
+// (LDS returns in order, so the compiler's own counted lgkmcnt waits for its k-fast reads only get more conservative.)
+template <bool KF>
+__device__ __forceinline__ void ring_frag_landed(bf16x8& f) {
+#ifndef CENET_HOSTSIM_BUILD
+  if (!KF) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f));
+#endif
+}
+
 // per-thread source description of one operand: NI = BX / 32 LDS-DMA instructions per thread and tile
 template <int NI>
 struct RingSrc {
@@ -141,6 +177,58 @@ __device__ __forceinline__ bf16x8 ring_mask_k(bf16x8 f, int kc, int lane, int kl
   return f;
 }
 
+// ---- in-kernel stamps: where a K-step spends its cycles (diagnostic build, -DCENET_RING_STAMPS; tools/ring_stamps.py) -----------
+// Each lap() reads the shader clock and adds the cycles since the previous lap to the segment just finished; the sums stay in
+// scalar registers and wave 0 of a few workgroups stores them once after the loop to a buffer of the caller's that nothing else
+// in the kernel reads.  The stamped build's fences forbid overlaps the product kernel has: read its SHARES, not its run time.
+// In the product build every member is empty and no clock read executes.
+enum { RSEG_WAIT = 0, RSEG_BARRIER, RSEG_ISSUE, RSEG_READS, RSEG_MFMA, RSEG_REST, RSEG_N };
+#if defined(CENET_RING_STAMPS) && !defined(CENET_HOSTSIM_BUILD)
+struct RingClock {
+  unsigned long long last, begin, cal, acc[RSEG_N], first[RSEG_N];
+  static __device__ __forceinline__ unsigned long long now() {
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+  }
+  __device__ __forceinline__ void start() {
+#pragma unroll
+    for (int i = 0; i < RSEG_N; ++i) acc[i] = first[i] = 0;
+    const unsigned long long t0 = now();
+    last = begin = now();
+    cal = last - t0;  // the cost of one stamp: every lap contains one
+  }
+  __device__ __forceinline__ void lap(int seg) {
+    const unsigned long long t = now();
+    acc[seg] += t - last;
+    last = t;
+  }
+  __device__ __forceinline__ void first_step_done() {
+#pragma unroll
+    for (int i = 0; i < RSEG_N; ++i) first[i] = acc[i];
+  }
+  // id: this workgroup of `total`; steps: loop trips it ran.  Record = acc[6], first[6], steps, loop cycles, stamp cost, id.
+  __device__ __forceinline__ void store(const GemmArgs& g, int id, int total, int steps, int tid) const {
+    if (g.stamps == nullptr || tid != 0) return;
+    const int stride = total > g.stamp_n ? total / g.stamp_n : 1;
+    const int slot = id / stride;
+    if (id != slot * stride || slot >= g.stamp_n) return;
+    unsigned long long* p = g.stamps + (long)slot * 16;
+#pragma unroll
+    for (int i = 0; i < RSEG_N; ++i) p[i] = acc[i], p[RSEG_N + i] = first[i];
+    p[12] = (unsigned long long)steps, p[13] = last - begin, p[14] = cal, p[15] = (unsigned long long)id;
+  }
+};
+#else
+struct RingClock {
+  __device__ __forceinline__ void start() {}
+  __device__ __forceinline__ void lap(int) {}
+  __device__ __forceinline__ void first_step_done() {}
+  __device__ __forceinline__ void store(const GemmArgs&, int, int, int, int) const {}
+};
+#endif
 template <bool AKF, bool BKF, int BM, int BN, int NS, bool SWAP>
 __global__ __launch_bounds__(256, (NS * (BM + BN) * 128 <= 80 * 1024 ? 2 : 1)) void gemm_ring_kernel(GemmArgs g) {
   constexpr int MI = BM / 32, NJ = BN / 32;
@@ -218,6 +306,8 @@ __global__ __launch_bounds__(256, (NS * (BM + BN) * 128 <= 80 * 1024 ? 2 : 1)) v
   for (int s = 0; s < NS - 1; ++s)
     if (s < T) issue(it0 + s, s);
 
+  RingClock clk;
+  clk.start();
   int cur = 0;
   for (int t = 0; t < T; ++t) {
     // tile t has landed once at most min(NS - 2, T - 1 - t) younger tiles are still outstanding
@@ -225,8 +315,11 @@ __global__ __launch_bounds__(256, (NS * (BM + BN) * 128 <= 80 * 1024 ? 2 : 1)) v
     if (NS >= 4 && young >= 2) ring_wait_vm<G * 2 <= 63 ? G * 2 : 0>();
     else if (NS >= 3 && young >= 1) ring_wait_vm<G>();
     else ring_wait_vm<0>();
+    clk.lap(RSEG_WAIT);
     ring_barrier();  // every wave's part of tile t is in LDS; every wave is done reading the buffer refilled below
+    clk.lap(RSEG_BARRIER);
     if (t + NS - 1 < T) issue(it0 + t + NS - 1, cur == 0 ? NS - 1 : cur - 1);
+    clk.lap(RSEG_ISSUE);
     const unsigned char* Ai = lds + cur * STAGE;
     const unsigned char* Bi = Ai + ABYTES;
     int klim_t = 64;
@@ -239,10 +332,14 @@ __global__ __launch_bounds__(256, (NS * (BM + BN) * 128 <= 80 * 1024 ? 2 : 1)) v
       bf16x8 a[MI], b[NJ];
 #pragma unroll
       for (int i = 0; i < MI; ++i)
-        a[i] = AKF ? ring_frag_kf(Ai, wm * (BM / 2) + i * 16, kc, lane) : ring_frag_rf<BM>(Ai, wm * (BM / 2) + i * 16, kc, lane);
+        a[i] = AKF ? ring_frag_kf(Ai, wm * (BM / 2) + i * 16, kc, lane) : ring_frag_rf_inflight<BM>(Ai, wm * (BM / 2) + i * 16, kc, lane);
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
-        b[j] = BKF ? ring_frag_kf(Bi, wn * (BN / 2) + j * 16, kc, lane) : ring_frag_rf<BN>(Bi, wn * (BN / 2) + j * 16, kc, lane);
+        b[j] = BKF ? ring_frag_kf(Bi, wn * (BN / 2) + j * 16, kc, lane) : ring_frag_rf_inflight<BN>(Bi, wn * (BN / 2) + j * 16, kc, lane);
+#pragma unroll
+      for (int i = 0; i < MI; ++i) ring_frag_landed<AKF>(a[i]);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) ring_frag_landed<BKF>(b[j]);
       if (klim_t < 64) {  // (wave-uniform; only the last K tile of an unaligned K)
         if (AKF) {
 #pragma unroll
@@ -259,15 +356,19 @@ __global__ __launch_bounds__(256, (NS * (BM + BN) * 128 <= 80 * 1024 ? 2 : 1)) v
 #pragma unroll
           for (int j = 0; j < 8; ++j) rsum[i] += cenet_bf2f((unsigned short)a[i][j]);
       }
+      clk.lap(RSEG_READS);
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int i = 0; i < MI; ++i)
           acc[i][j] = SWAP ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0)
                            : __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+      clk.lap(RSEG_MFMA);
     }
+    if (t == 0) clk.first_step_done();
     cur = cur + 1 == NS ? 0 : cur + 1;
   }
+  clk.store(g, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), gridDim.x * gridDim.y * gridDim.z, T, tid);
   if (do_asum) {
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
@@ -341,15 +442,19 @@ __global__ __launch_bounds__(256, 2) void gemm_ring_stream_kernel(GemmArgs g, in
   Where cur = where(tile_of(vt));
   issue(cur, 0);
   ring_wait_vm<0>();
-  int set = 0;
-  for (; vt < total_tiles; vt += gridDim.x, set ^= 1) {
+  RingClock clk;
+  clk.start();
+  int set = 0, trips = 0;
+  for (; vt < total_tiles; vt += gridDim.x, set ^= 1, ++trips) {
     ring_barrier();  // every wave's part of this tile has landed (each waited for its own); everybody is done with the other set
+    clk.lap(RSEG_BARRIER);
     const int nvt = vt + gridDim.x;
     Where nxt = cur;
     if (nvt < total_tiles) {
       nxt = where(tile_of(nvt));
       issue(nxt, set ^ 1);
     }
+    clk.lap(RSEG_ISSUE);
     f32x4 acc[MI][NJ];
 #pragma unroll
     for (int i = 0; i < MI; ++i)
@@ -364,22 +469,32 @@ __global__ __launch_bounds__(256, 2) void gemm_ring_stream_kernel(GemmArgs g, in
         bf16x8 a[MI], b[NJ];
 #pragma unroll
         for (int i = 0; i < MI; ++i)
-          a[i] = AKF ? ring_frag_kf(Ai, wm * 32 + i * 16, kc, lane) : ring_frag_rf<BM>(Ai, wm * 32 + i * 16, kc, lane);
+          a[i] = AKF ? ring_frag_kf(Ai, wm * 32 + i * 16, kc, lane) : ring_frag_rf_inflight<BM>(Ai, wm * 32 + i * 16, kc, lane);
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
-          b[j] = BKF ? ring_frag_kf(Bi, wn * 32 + j * 16, kc, lane) : ring_frag_rf<BN>(Bi, wn * 32 + j * 16, kc, lane);
+          b[j] = BKF ? ring_frag_kf(Bi, wn * 32 + j * 16, kc, lane) : ring_frag_rf_inflight<BN>(Bi, wn * 32 + j * 16, kc, lane);
+#pragma unroll
+        for (int i = 0; i < MI; ++i) ring_frag_landed<AKF>(a[i]);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) ring_frag_landed<BKF>(b[j]);
+        clk.lap(RSEG_READS);
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
           for (int i = 0; i < MI; ++i)
             acc[i][j] = SWAP ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0)
                              : __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+        clk.lap(RSEG_MFMA);
       }
     }
     ring_wait_vm<0>();  // the next tile's loads (issued a whole tile ago) and the PREVIOUS tile's stores; not this tile's stores
+    clk.lap(RSEG_WAIT);
     gemm_epilogue<bf16_t, BM, BN, SWAP, false>(g, acc, (float*)nullptr, cur.m0, cur.n0, cur.bo, cur.bi, cur.batch, wave, lane);
+    clk.lap(RSEG_REST);  // the epilogue's address arithmetic and store issue
+    if (trips == 0) clk.first_step_done();
     cur = nxt;
   }
+  clk.store(g, blockIdx.x, gridDim.x, trips, tid);
 }
 
 template <bool AKF, bool BKF, bool SWAP>
