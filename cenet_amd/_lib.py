@@ -6,7 +6,9 @@ check kernel logic without a GPU; nothing in the package does that.)
 
 include/cenet_hip.h is the one declaration of the C ABI: `parse_header` reads the five argument structs and every prototype
 from it, `bind` gives each entry point of a loaded library its `restype` / `argtypes`.  Callers pass plain Python values; a
-missing argument or one of the wrong kind raises instead of launching.
+missing argument or one of the wrong kind raises instead of launching.  ctypes sees every data pointer as `void*`; what a pointer
+points AT is kept beside the prototypes (`PARAMS`), and cenet_amd/kern.py holds the tensors of every launch to it.  This module
+stays free of torch.
 """
 from __future__ import annotations
 
@@ -30,25 +32,30 @@ _STRUCTS = {"cenet_mat_t": "MatT", "cenet_epi_t": "EpiT", "cenet_wgrad_prob_t": 
             "cenet_diffattn_t": "DiffAttnT"}
 
 
+PTR_PTR, STRUCT_PTR = "**", "struct*"  # parameter kinds that take no tensor: an array of pointers, an argument struct
+
+
 def _ctype(decl: str, structs, where: str):
-    """(ctypes type, name) of one declarator with its type, `const float* const* x` or `long sb`"""
+    """(ctypes type, name, kind) of one declarator with its type, `const float* const* x` or `long sb`; kind: the pointee
+    spelling of a single-level data pointer ("float", "unsigned short", ...), PTR_PTR, STRUCT_PTR, None for a scalar"""
     toks = decl.replace("*", " * ").split()
     words = [t for t in toks if t not in ("*", "const")]
     if len(words) < 2 or toks[-1] != words[-1] or words[-1] in _TYPE_WORDS:  # (every parameter and field is named)
         raise ValueError(f"cenet_hip.h: cannot read `{decl.strip()}` in {where}")
     base, stars = " ".join(words[:-1]), toks.count("*")
     if stars == 0 and base in _SCALARS:
-        return _SCALARS[base], words[-1]
+        return _SCALARS[base], words[-1], None
     if stars == 1 and base in structs:
-        return C.POINTER(structs[base]), words[-1]
+        return C.POINTER(structs[base]), words[-1], STRUCT_PTR
     if stars and base in _POINTEES:
-        return C.c_void_p, words[-1]
+        return C.c_void_p, words[-1], (base if stars == 1 else PTR_PTR)
     raise ValueError(f"cenet_hip.h: unknown type `{decl.strip()}` in {where}")
 
 
 def parse_header(text: str):
-    """(structs, protos) of a header text: {C struct name: ctypes.Structure subclass} for the `typedef struct { ... } name;`
-    bodies and {symbol: (restype, [argtypes])} for the prototypes.  A spelling it does not know raises; it never guesses."""
+    """(structs, protos, params) of a header text: {C struct name: ctypes.Structure subclass} for the `typedef struct { ... } name;`
+    bodies, {symbol: (restype, [argtypes])} for the prototypes and {symbol: ((parameter name, kind), ...)} with the kinds of
+    `_ctype`.  A spelling it does not know raises; it never guesses."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
     structs = {}
@@ -57,30 +64,30 @@ def parse_header(text: str):
         body, cname, fields = m.group(1), m.group(2), []
         for decl in filter(str.strip, body.split(";")):  # `type a, b, *c`
             first, *rest = decl.split(",")
-            ct, name = _ctype(first, {}, cname)
-            fields.append((name, ct))
             base = " ".join(first.replace("*", " * ").split()[:-1]).rstrip("* ")
-            fields += [_ctype(f"{base} {d}", {}, cname)[::-1] for d in rest]
+            fields += [_ctype(d, {}, cname)[1::-1] for d in (first, *(f"{base} {d}" for d in rest))]
         structs[cname] = type(_STRUCTS.get(cname, cname), (C.Structure,),
                               {"_fields_": fields, "__doc__": f"{cname} (include/cenet_hip.h)."})
         return " "
 
     text = re.sub(r"typedef\s+struct\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
     text = re.sub(r"typedef[^;]*;", " ", text)
-    protos = {}
+    protos, params_of = {}, {}
     for ret, name, params in re.findall(r"([^;{}()]+?)\b(\w+)\s*\(([^()]*)\)\s*;", text):
         ret = " ".join(ret.replace("*", " * ").split())
         if ret not in _RETURNS:
             raise ValueError(f"cenet_hip.h: unknown return type `{ret}` of {name}")
         params = [] if params.strip() in ("", "void") else params.split(",")
-        proto = (_RETURNS[ret], [_ctype(p, structs, name)[0] for p in params])
+        decls = [_ctype(p, structs, name) for p in params]
+        proto = (_RETURNS[ret], [d[0] for d in decls])
         if protos.setdefault(name, proto) != proto:
             raise ValueError(f"cenet_hip.h: {name} is declared twice, differently")
-    return structs, protos
+        params_of[name] = tuple(d[1:] for d in decls)
+    return structs, protos, params_of
 
 
 with open(HEADER_PATH) as _f:
-    _STRUCT_TYPES, PROTOS = parse_header(_f.read())
+    _STRUCT_TYPES, PROTOS, PARAMS = parse_header(_f.read())
 MatT, EpiT, WgradProbT, AttnT, DiffAttnT = (_STRUCT_TYPES[c] for c in _STRUCTS)
 
 

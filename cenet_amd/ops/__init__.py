@@ -1,7 +1,9 @@
 """cenet_amd.ops — autograd operators of the CENet hot path, forward AND backward on hand-written HIP kernels.
 
-One module per operator family (round 6: the former 3 100-line ops.py), imported here in dependency order; every public and private name is
-re-exported, so `from cenet_amd import ops; ops.linear(...)` / `ops._WgradCfg` / `ops._ZeroWs` read as they always did:
+One module per operator family (round 6: cut out of one 3 100-line module).  Each module imports by name what it uses from the module that
+defines it and lists in `__all__` the names it defines: the public ones and the private ones that other modules, tests, tools or
+bench.py reach.  This package re-exports exactly those lists, so `from cenet_amd import ops; ops.linear(...)` / `ops._WgradCfg` /
+`ops._ZeroWs` read as they always did (torch, os and the like are not among them):
   ops.infra          shared plumbing of the operator modules: tensor allocation helpers, zero-at-rest workspaces, parameter / gradient views into the
   ops.linear         GEMM-backed operators: Linear / MultiLinear in token layout, 1x1 convolutions on NCHW, dense k x k convolutions (implicit GEMM, direct
   ops.norm           LayerNorm over the last dimension and train-mode BatchNorm (+ fused activation)
@@ -12,6 +14,8 @@ re-exported, so `from cenet_amd import ops; ops.linear(...)` / `ops._WgradCfg` /
   ops.gates          CCU and SRM gates (cfam.py:251-264, 93-101)
   ops.dseb_loss      DSEB combine (dseb.py:40-50,63-76,156-163) and the fused segmentation loss (utils/core.py:44-131,161-188)
 """
+import sys
+
 from .infra import *  # noqa: F401,F403
 from .linear import *  # noqa: F401,F403
 from .norm import *  # noqa: F401,F403
@@ -22,4 +26,7 @@ from .decoder_fused import *  # noqa: F401,F403
 from .gates import *  # noqa: F401,F403
 from .dseb_loss import *  # noqa: F401,F403
 
-__all__ = [n for n in dir() if not n.startswith("__")]
+# (through sys.modules: `ops.linear`, `ops.norm`, ... are what the modules of those names export, not the modules)
+__all__ = [n for m in ("infra", "linear", "norm", "depthwise", "attention", "glue", "decoder_fused", "gates", "dseb_loss")
+           for n in sys.modules[f"{__name__}.{m}"].__all__]
+del sys

@@ -1,20 +1,13 @@
 """cenet_amd.ops.attention — attention operators: spatial-reduction attention, Non-local attention, differential attention heads + combine.
-Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` exposes every name as before)."""
+Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` re-exports the names in `__all__`)."""
 from __future__ import annotations
 
-import contextlib
-import math
-import os
-from typing import Optional, Sequence
-
 import torch
+from torch import Tensor
 from torch.autograd import Function
 
 from .. import kern
-from .infra import *  # noqa: F401,F403
-from .linear import *  # noqa: F401,F403
-from .norm import *  # noqa: F401,F403
-from .depthwise import *  # noqa: F401,F403
+from .infra import _ZeroWs, _act, _bf, _c, _empty, _zeros, grad_buf
 
 
 # =====================================================================================================
@@ -466,4 +459,5 @@ def diff_attention_combine(U, lq1, lk1, lq2, lk2, lambda_init):
     return DiffAttnCombineFn.apply(U, lq1, lk1, lq2, lk2, lambda_init)
 
 
-__all__ = [n for n in dir() if not n.startswith("__")]
+__all__ = ["SRAttentionFn", "NonlocalAttnFn", "DiffAttnHeadsFn", "sr_attention", "nonlocal_attention", "NonlocalAttnJointFn",
+           "nonlocal_attention_joint", "diff_attention_heads", "DiffAttnCombineFn", "diff_attention_combine", "_OffsetView"]

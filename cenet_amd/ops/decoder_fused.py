@@ -1,23 +1,17 @@
 """cenet_amd.ops.decoder_fused — resampling operators and the channel-local fused chains of the decoder and the head (csrc/chanloc.hip, csrc/res_tail.hip): EUCB front,
 CFAM front / mid, pooled branch, residual-block tails.
-Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` exposes every name as before)."""
+Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` re-exports the names in `__all__`)."""
 from __future__ import annotations
 
-import contextlib
 import math
 import os
-from typing import Optional, Sequence
 
 import torch
+from torch import Tensor
 from torch.autograd import Function
 
 from .. import kern
-from .infra import *  # noqa: F401,F403
-from .linear import *  # noqa: F401,F403
-from .norm import *  # noqa: F401,F403
-from .depthwise import *  # noqa: F401,F403
-from .attention import *  # noqa: F401,F403
-from .glue import *  # noqa: F401,F403
+from .infra import _Batch1, _act, _bf, _c, _empty, _gb, _grad_pair, _mom, bn_momentum, grad_buf
 
 
 # =====================================================================================================
@@ -120,11 +114,8 @@ class EucbFrontFn(Function):
         g = _c(g)
         B, Cn, H, Wd = x.shape
         dx = torch.empty_like(x)
-        dw, dg, db = grad_buf(wp), grad_buf(gp), grad_buf(bp)
-        if dw is None:
-            dw = _zeros(w.shape, x)
-        if dg is None:
-            dg, db = _zeros((Cn,), x), _zeros((Cn,), x)
+        dw = _gb(wp, x)
+        dg, db = _grad_pair(gp, bp, x, (Cn,))
         kern.eucb_bwd(g, x, w, gamma, beta, eps, slope, mean, var, dx, dw, dg, db, B, Cn, H, Wd)
         return (dx,) + (None,) * 9
 
@@ -527,4 +518,7 @@ def res_tail_pool_supported(x2, x3, bn2, bn3, w) -> bool:
                 and w.numel() == x2.shape[1] and os.environ.get("CENET_RES_TAIL_FUSED", "1") != "0")
 
 
-__all__ = [n for n in dir() if not n.startswith("__")]
+__all__ = ["BilinearFn", "interpolate_bilinear", "Nearest2xFn", "nearest2x", "EucbFrontFn", "eucb_front_supported", "eucb_front", "CfamMidFn",
+           "cfam_mid_supported", "cfam_mid", "CfamFrontFn", "cfam_front_supported", "cfam_front", "PoolBranchFn", "JoinBnPoolFn", "join_bn_pool",
+           "pool_branch_supported", "pool_branch", "AdaptiveAvgPoolFn", "adaptive_avgpool", "MaxPool2ScaleFn", "maxpool2_scale", "ResTailPoolFn",
+           "res_tail_pool", "ResTailImgPoolFn", "res_tail_img_pool", "res_tail_img_pool_supported", "res_tail_pool_supported"]

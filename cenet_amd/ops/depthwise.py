@@ -1,19 +1,14 @@
 """cenet_amd.ops.depthwise — depthwise 3x3 convolutions (token layout and NCHW) and the fused PVT Mlp half (csrc/pvt_mlp.hip).
-Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` exposes every name as before)."""
+Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` re-exports the names in `__all__`)."""
 from __future__ import annotations
 
-import contextlib
-import math
 import os
-from typing import Optional, Sequence
 
 import torch
 from torch.autograd import Function
 
 from .. import kern
-from .infra import *  # noqa: F401,F403
-from .linear import *  # noqa: F401,F403
-from .norm import *  # noqa: F401,F403
+from .infra import _WgradCfg, _c, _empty, _gb, _grad_pair, _prescaled_put, _wgrad_rows, _wgrad_side, grad_buf
 
 
 # =====================================================================================================
@@ -105,26 +100,10 @@ class PvtMlpFn(Function):
         HD = w1.shape[0]
         R = B * N
 
-        def wgrad(gy, xin, Wp, bp, Nn, K):
-            dW, db = grad_buf(Wp), grad_buf(bp)
-            if dW is not None and _wgrad_deferrable(Nn, K, gy, xin, K=R):
-                _wgrad_defer(gy, 0, Nn, 0, xin, 0, K, 0, dW, 0, db, Nn, K, R, 1, 0)
-            elif dW is not None or db is not None:
-                with _wgrad_side(gy, xin):
-                    if dW is not None:
-                        kern.gemm(kern.mat_plain(gy, 1, Nn, kfast=0), kern.mat_plain(xin, K, 1, kfast=0), dW, Nn, K, R, scr=K,
-                                  scc=1, splits=kern.pick_splits(Nn, K, 1, (R + 31) // 32), atomic=True, asum=db)
-                    else:
-                        kern.col_sum(gy, db, R, Nn)
-
         # two kernels: (scale + fc2 data gradient + depthwise / GELU backward) and (depthwise data gradient + fc1 data gradient +
         # LayerNorm backward with the residual connection), csrc/pvt_mlp.hip
-        dwd, dbd = grad_buf(wd), grad_buf(bd)
-        if dwd is None:
-            dwd, dbd = _zeros(wd.shape, x), _zeros(bd.shape, x)
-        dg, db = grad_buf(ln_g), grad_buf(ln_b)
-        if dg is None:
-            dg, db = _zeros((Cn,), x), _zeros((Cn,), x)
+        dwd, dbd = _grad_pair(wd, bd, x, wd.shape, bd.shape)
+        dg, db = _grad_pair(ln_g, ln_b, x, (Cn,))
         gu, dh, dx = torch.empty_like(a), torch.empty_like(a), torch.empty_like(x)
         dxs = None
         if ctx.up_scale is not None and _WgradCfg.prescale and ctx.up_scale.numel() == B:
@@ -135,8 +114,8 @@ class PvtMlpFn(Function):
                          grad_buf(b2), B, H, Wd, Cn, HD, up_scale=ctx.up_scale if dxs is not None else None, dxs=dxs)
         # a was saved as s_b * GELU(.): dW2 = (s_b g)^T a = g^T (s_b a), no scaled copy of g; the bias gradient (column sums of
         # s_b g) comes from the second kernel, so the recorded problem carries no bias
-        wgrad(g, a, w2, None, Cn, HD)
-        wgrad(dh, xn, w1, b1, HD, Cn)
+        _wgrad_rows(g, a, w2, None, Cn, HD, R)
+        _wgrad_rows(dh, xn, w1, b1, HD, Cn, R)
         return (dx,) + (None,) * 13
 
 
@@ -223,4 +202,4 @@ def dwconv_nchw(x, w, b=None, dil=1, act="none"):
     return DWConvNCHWFn.apply(x, w, b, dil, act)
 
 
-__all__ = [n for n in dir() if not n.startswith("__")]
+__all__ = ["DWConvTokFn", "PvtMlpFn", "pvt_mlp_supported", "pvt_mlp", "DWConvNCHWFn", "DWActFn", "dwconv_tok", "dwconv_nchw"]

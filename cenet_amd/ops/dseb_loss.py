@@ -1,24 +1,15 @@
 """cenet_amd.ops.dseb_loss — DSEB combine (dseb.py:40-50,63-76,156-163) and the fused segmentation loss (utils/core.py:44-131,161-188).
-Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` exposes every name as before)."""
+Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` re-exports the names in `__all__`)."""
 from __future__ import annotations
 
-import contextlib
-import math
-import os
 from typing import Optional, Sequence
 
 import torch
+from torch import Tensor
 from torch.autograd import Function
 
 from .. import kern
-from .infra import *  # noqa: F401,F403
-from .linear import *  # noqa: F401,F403
-from .norm import *  # noqa: F401,F403
-from .depthwise import *  # noqa: F401,F403
-from .attention import *  # noqa: F401,F403
-from .glue import *  # noqa: F401,F403
-from .decoder_fused import *  # noqa: F401,F403
-from .gates import *  # noqa: F401,F403
+from .infra import _c, _empty, _zeros, grad_buf
 
 
 # =====================================================================================================
@@ -186,4 +177,4 @@ def seg_loss(logits, labels, *, w_dice=0., w_ce=0., w_boundary=0., w_jaccard=0.,
     return SegLossExFn.apply(logits, labels, cw, cfg)
 
 
-__all__ = [n for n in dir() if not n.startswith("__")]
+__all__ = ["DsebCombineFn", "dseb_combine", "DiceCELossFn", "dice_ce_loss", "SegLossExFn", "class_weight_buffer", "seg_loss"]

@@ -1,23 +1,12 @@
 """cenet_amd.ops.gates — CCU and SRM gates (cfam.py:251-264, 93-101).
-Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` exposes every name as before)."""
+Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` re-exports the names in `__all__`)."""
 from __future__ import annotations
-
-import contextlib
-import math
-import os
-from typing import Optional, Sequence
 
 import torch
 from torch.autograd import Function
 
 from .. import kern
-from .infra import *  # noqa: F401,F403
-from .linear import *  # noqa: F401,F403
-from .norm import *  # noqa: F401,F403
-from .depthwise import *  # noqa: F401,F403
-from .attention import *  # noqa: F401,F403
-from .glue import *  # noqa: F401,F403
-from .decoder_fused import *  # noqa: F401,F403
+from .infra import _Batch1, _c, _empty, _grad_pair, grad_buf
 
 
 # =====================================================================================================
@@ -78,19 +67,15 @@ class CCUFn(Function):
             if not training:
                 raise RuntimeError("CCU backward needs training-mode BatchNorm")
             dz = torch.empty_like(dzn)
-            dg, db = grad_buf(ctx.refs[2]), grad_buf(ctx.refs[3])
-            if kern.bn1d_supported(B):
-                kern.bn1d_bwd(dzn, z, dz, mean, var, 1e-5, bn_w, dg, db, B, Cn)  # (one launch; NULL gradients: frozen affine)
+            if kern.bn1d_supported(B):  # (one launch; NULL gradients: frozen affine)
+                kern.bn1d_bwd(dzn, z, dz, mean, var, 1e-5, bn_w, grad_buf(ctx.refs[2]), grad_buf(ctx.refs[3]), B, Cn)
             else:
                 ws = _empty((2 * Cn * 256,), x)  # CENET_BN_WS_FLOATS(C)
-                if dg is None:
-                    dg, db = _zeros((Cn,), x), _zeros((Cn,), x)
+                dg, db = _grad_pair(ctx.refs[2], ctx.refs[3], x, (Cn,))
                 kern.bn_bwd(dzn, Cn, z, Cn, dz, Cn, mean, var, 1e-5, bn_w, bn_b, "none", 0.0, B, Cn, 1, ws, dg, db)
         else:
             dz = dzn
-        d1, d2 = grad_buf(ctx.refs[0]), grad_buf(ctx.refs[1])
-        if d1 is None:
-            d1, d2 = _zeros(fc1.shape, x), _zeros(fc2.shape, x)
+        d1, d2 = _grad_pair(ctx.refs[0], ctx.refs[1], x, fc1.shape, fc2.shape)
         dx = torch.empty_like(x)
         kern.ccu_bwd_apply(x, g, zn, dz, u, amax, fc1, fc2, d1, d2, dx, B, Cn, HW, dx_add=g_tap)
         return (dx,) + (None,) * 9
@@ -152,13 +137,9 @@ class SRMFn(Function):
         HW = H * Wd
         dfb = torch.empty_like(f)
         kern.gate_pix_bwd_reduce(x, g, fb, dfb, B, Cn, HW)
-        dg, db = grad_buf(ctx.refs[2]), grad_buf(ctx.refs[3])
-        if dg is None:
-            dg, db = _zeros((1,), x), _zeros((1,), x)
+        dg, db = _grad_pair(ctx.refs[2], ctx.refs[3], x, (1,))
         du = torch.empty_like(u)
-        dp, dd = grad_buf(ctx.refs[0]), grad_buf(ctx.refs[1])
-        if dp is None:
-            dp, dd = _zeros(pwc.shape, x), _zeros(dwc.shape, x)
+        dp, dd = _grad_pair(ctx.refs[0], ctx.refs[1], x, pwc.shape, dwc.shape)
         if ctx.fused:
             part2 = _empty((kern.srm_parts(B, H, Wd), 2), x)
             kern.srm_conv_bn_bwd(u, dfb, fa, f, mean, var, 1e-5, bn_w, pwc, dwc, part2, du, dp, dd, dg, db, B, H, Wd)
@@ -178,4 +159,4 @@ def srm(x, pwc, dwc, bn_w, bn_b, bn_rm, bn_rv, bn_nbt, training):
     return SRMFn.apply(x, pwc, dwc, bn_w, bn_b, bn_rm, bn_rv, bn_nbt, training)
 
 
-__all__ = [n for n in dir() if not n.startswith("__")]
+__all__ = ["CCUFn", "ccu", "SRMFn", "srm"]

@@ -1,22 +1,13 @@
 """cenet_amd.ops.glue — layout / glue operators: token <-> NCHW, concat / split (+ merged depthwise branches), grouped 1x1, add + activation, SiLU product,
 residual mix, layer-scale residual.
-Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` exposes every name as before)."""
+Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` re-exports the names in `__all__`)."""
 from __future__ import annotations
-
-import contextlib
-import math
-import os
-from typing import Optional, Sequence
 
 import torch
 from torch.autograd import Function
 
 from .. import kern
-from .infra import *  # noqa: F401,F403
-from .linear import *  # noqa: F401,F403
-from .norm import *  # noqa: F401,F403
-from .depthwise import *  # noqa: F401,F403
-from .attention import *  # noqa: F401,F403
+from .infra import _act, _bf, _c, _empty, _gb, _wgrad_side, _zeros, grad_buf
 
 
 # =====================================================================================================
@@ -495,4 +486,6 @@ def scale_residual(x, y, ls):
     return ScaleResidualFn.apply(x, y, ls)
 
 
-__all__ = [n for n in dir() if not n.startswith("__")]
+__all__ = ["TokToNCHWFn", "tok_to_nchw", "Concat2Fn", "concat2", "Add2Fn", "add2", "SplitChannelsFn", "split_channels", "SplitDWFn", "split_dwconv",
+           "SplitDWBnFn", "split_dwconv_bn_supported", "split_dwconv_bn", "GroupedConv1x1Fn", "grouped_conv1x1", "ConcatFn", "concat", "AddActFn",
+           "add_act", "SiluMulFn", "silu_mul", "MixFn", "mix", "ScaleResidualFn", "scale_residual"]

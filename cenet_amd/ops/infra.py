@@ -15,16 +15,14 @@ Reference file:line citations are relative to /root/reference/src/.
 from __future__ import annotations
 
 import contextlib
-import math
 import os
-from typing import Optional, Sequence
+from typing import Optional
 
 import torch
+from torch import Tensor
 from torch.autograd import Function
 
 from .. import kern
-
-Tensor = torch.Tensor
 
 
 def _empty(shape, ref: Tensor, dtype=torch.float32) -> Tensor:
@@ -441,6 +439,25 @@ def _wgrad_deferrable(M: int, N: int, *ts, K: int = 1, nkb: int = 1) -> bool:
                 and all(t.dtype == torch.bfloat16 and t.numel() < (1 << 31) for t in ts))
 
 
+def _wgrad_rows(gy: Tensor, x: Tensor, Wp: Optional[Tensor], bp: Optional[Tensor], N: int, K: int, R: int, returned=None):
+    """the weight gradient of a row-major Linear, dW[N, K] += gy[R, N]^T x[R, K] and db[N] += column sums of gy, into the
+    gradient buffers of Wp / bp (either may be frozen or absent): recorded for the grouped launch where that takes it, else
+    launched on the weight-gradient stream with the bias gradient riding along (asum), else the column sums alone.
+    returned: as _wgrad_side"""
+    dW, db = grad_buf(Wp), grad_buf(bp)
+    if dW is not None and _wgrad_deferrable(N, K, gy, x, K=R):
+        # recorded, not launched: reduced with the other weight gradients of the segment by one grouped launch
+        _wgrad_defer(gy, 0, N, 0, x, 0, K, 0, dW, 0, db, N, K, R, 1, 0)
+    elif dW is not None or db is not None:
+        with _wgrad_side(gy, x, returned=returned):
+            if dW is not None:
+                # the bias gradient (column sums of the output gradient) rides in the weight-gradient pass (asum)
+                kern.gemm(kern.mat_plain(gy, 1, N, kfast=0), kern.mat_plain(x, K, 1, kfast=0), dW, N, K, R, scr=K, scc=1,
+                          splits=kern.pick_splits(N, K, 1, (R + 31) // 32), atomic=True, asum=db)
+            else:
+                kern.col_sum(gy, db, R, N)
+
+
 _graph_task_id = getattr(torch._C, "_current_graph_task_id", None)
 
 
@@ -567,6 +584,19 @@ def _gb(p, ref):
     return g if g is not None else _zeros(p.shape, ref)
 
 
+def _grad_pair(p, q, ref, shape, shape_q=None):
+    """gradient buffers of a pair of parameters that one kernel adds into together (the gamma / beta of a norm, the two
+    weights of a gate): (grad_buf(p), grad_buf(q)), or fp32 scratch of `shape` / `shape_q` (default: `shape`) for BOTH when p is
+    frozen or absent.
+    The pair goes by its FIRST member: with p frozen and q trainable, q's gradient lands in the scratch and is dropped (a
+    frozen gamma beside a trainable beta).  The network never freezes one without the other; a fix belongs to a change of
+    its own."""
+    dp, dq = grad_buf(p), grad_buf(q)
+    if dp is None:
+        dp, dq = _zeros(shape, ref), _zeros(shape if shape_q is None else shape_q, ref)
+    return dp, dq
+
+
 def bn_momentum(bn) -> float:
     """the running-statistics factor of a BatchNorm container.  momentum=None means a CUMULATIVE moving average in PyTorch (factor
     1 / num_batches_tracked); no kernel here implements that and the reference never builds such a layer (every BatchNorm of
@@ -597,4 +627,8 @@ def batch1_semantics(on: bool = True):
         _Batch1.on = old
 
 
-__all__ = [n for n in dir() if not n.startswith("__")]
+__all__ = ["grad_buf", "merged_param", "refresh_member_shadows", "merged_buffer", "set_branch_streams", "branch_stream",
+           "branch_gate_enabled", "BranchGate", "branch_streams", "set_wgrad_overlap", "wgrad_stream", "wgrad_join", "set_wgrad_grouping",
+           "wgrad_hold", "wgrad_pending", "tag_bscale", "wgrad_flush", "bn_momentum", "batch1_semantics", "_empty", "_act", "_bf", "_acc32",
+           "_zeros", "_ZeroWs", "_WgradCfg", "_WgradState", "_WG", "_wgrad_side", "_wgrad_deferrable", "_wgrad_rows", "_wgrad_defer", "_ln_bwd",
+           "_prescaled_put", "_prescaled_take", "_c", "_gb", "_grad_pair", "_mom", "_Batch1"]

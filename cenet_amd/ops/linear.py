@@ -1,18 +1,16 @@
 """cenet_amd.ops.linear — GEMM-backed operators: Linear / MultiLinear in token layout, 1x1 convolutions on NCHW, dense k x k convolutions (implicit GEMM, direct
 kernels, token patch rows), the spatial-reduction conv + LayerNorm.
-Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` exposes every name as before)."""
+Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` re-exports the names in `__all__`)."""
 from __future__ import annotations
 
 import contextlib
-import math
-import os
-from typing import Optional, Sequence
 
 import torch
 from torch.autograd import Function
 
 from .. import kern
-from .infra import *  # noqa: F401,F403
+from .infra import (_ZeroWs, _acc32, _act, _bf, _c, _prescaled_take, _wgrad_defer, _wgrad_deferrable, _wgrad_rows, _wgrad_side, _zeros, grad_buf,
+                    tag_bscale)
 
 
 # =====================================================================================================
@@ -83,19 +81,7 @@ class LinearFn(Function):
             if gs is None:
                 gs = torch.empty_like(g)
                 kern.scale_batch(g, bscale, gs, x.shape[0], g.numel() // x.shape[0])
-        dW, db = grad_buf(Wp), grad_buf(bp)
-        if dW is not None and _wgrad_deferrable(N, K, gs, x, K=R):
-            # recorded, not launched: reduced with the other weight gradients of the segment by one grouped launch
-            _wgrad_defer(gs, 0, N, 0, x, 0, K, 0, dW, 0, db, N, K, R, 1, 0)
-        elif dW is not None or db is not None:
-            with _wgrad_side(gs, x, returned=(g if ctx.has_resid and gs is g else None)):
-                if dW is not None:
-                    # the bias gradient (column sums of the output gradient) rides in the weight-gradient pass (asum)
-                    iters = (R + 31) // 32
-                    kern.gemm(kern.mat_plain(gs, 1, N, kfast=0), kern.mat_plain(x, K, 1, kfast=0), dW, N, K, R, scr=K, scc=1,
-                              splits=kern.pick_splits(N, K, 1, iters), atomic=True, asum=db)
-                elif db is not None:
-                    kern.col_sum(gs, db, R, N)
+        _wgrad_rows(gs, x, Wp, bp, N, K, R, returned=(g if ctx.has_resid and gs is g else None))
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
@@ -289,21 +275,17 @@ class Conv2dFn(Function):
         plain_nchw = (sb == Cin * H * Wd and sc == H * Wd and sy == Wd and sx == 1 and out_layout == "nchw" and b is None)
         ctx.direct = bool(plain_nchw and _bf(x) and kern.conv_direct_supported(Cin, Cout, k, stride, pad))
         ctx.c1 = bool(plain_nchw and _bf(x) and not ctx.direct and kern.conv_c1_supported(Cin, Cout, k, stride, pad))
+        ctx.save_for_backward(x, W)
+        ctx.refs = (W, b)
+        ctx.geom = geom
+        ctx.out_hw = (Ho, Wo)
         if ctx.c1:  # bf16, the two convolutions that read the one-channel network input (conv_c1.hip)
             y = _act((B, Cout, Ho, Wo), x)
             kern.conv_c1_fwd(x, W, y, B, Cout, H, Wd, k)
-            ctx.save_for_backward(x, W)
-            ctx.refs = (W, b)
-            ctx.geom = geom
-            ctx.out_hw = (Ho, Wo)
             return y
         if ctx.direct:  # bf16 tensors, output-head convs: LDS-halo direct convolution (conv_direct.hip)
             y = _act((B, Cout, Ho, Wo), x)
             kern.conv_direct(x, W, y, B, Cin, Cout, H, Wd, k, 0)
-            ctx.save_for_backward(x, W)
-            ctx.refs = (W, b)
-            ctx.geom = geom
-            ctx.out_hw = (Ho, Wo)
             return y
         Bm = kern.mat_im2col(x, sb=sb, skb=0, sci=sc, sy=sy, sx=sx, KH=k, KW=k, Pw=Wo, Hs=H, Ws=Wd, stride=stride,
                              pad=pad, dil=1, patch_is_row=1, transposed=0, kfast=0)
@@ -325,10 +307,6 @@ class Conv2dFn(Function):
             y = _act(shape, x)
             kern.gemm(kern.mat_plain(Wq, Kd, 1, kfast=1), Bm, y, Cout, Ho * Wo, Kd, scr=scr, scc=scc, scb=Cout * Ho * Wo,
                       nbatch=B, bias=b, bias_on_row=True)
-        ctx.save_for_backward(x, W)
-        ctx.refs = (W, b)
-        ctx.geom = geom
-        ctx.out_hw = (Ho, Wo)
         return y
 
     @staticmethod
@@ -482,13 +460,20 @@ class Im2colTokFn(Function):
         return dx, None, None, None, None, None
 
 
+def patch_rows_conv(W, N, H, Wd, stride, pad=0) -> bool:
+    """the conv cuts the H x W token map (N tokens) into NON-OVERLAPPING patch rows: a k x k kernel of stride k, k in {2, 4, 8},
+    no padding, k dividing H and W — PatchTokFn gathers the rows, the conv is then a Linear layer over them"""
+    k = W.shape[2]
+    return bool(k == stride and W.shape[3] == k and pad == 0 and k in (2, 4, 8) and H % k == 0 and Wd % k == 0 and N == H * Wd
+                and W.is_contiguous())
+
+
 def conv2d_tok(x, H, Wd, W, b=None, stride=1, pad=0, out_layout="tok"):
     """x [B, H*W, C] token layout read as an NCHW map (pvtv2.py:93-94)."""
     x = _c(x)
     B, N, C = x.shape
     k = W.shape[2]
-    if (out_layout == "tok" and k == stride and W.shape[3] == k and pad == 0 and k in (2, 4, 8) and H % k == 0
-            and Wd % k == 0 and N == H * Wd and W.is_contiguous()):
+    if out_layout == "tok" and patch_rows_conv(W, N, H, Wd, stride, pad):
         # non-overlapping patches (the spatial-reduction conv): gather the patches once, then it is a Linear layer over
         # rows of C*k*k with the weight in its own [Cout, (c, ky, kx)] order -- both GEMM operands k-contiguous
         return linear(PatchTokFn.apply(x, H, Wd, k), W, b, split_k=True)
@@ -500,4 +485,5 @@ def conv2d_tok(x, H, Wd, W, b=None, stride=1, pad=0, out_layout="tok"):
     return Conv2dFn.apply(x, W, b, geom)
 
 
-__all__ = [n for n in dir() if not n.startswith("__")]
+__all__ = ["LinearFn", "linear", "MultiLinearFn", "multi_linear", "Conv1x1Fn", "conv1x1", "Conv2dFn", "ChanSumWeightFn", "chan_sum_weight",
+           "conv2d_nchw", "PatchTokFn", "Im2colTokFn", "patch_rows_conv", "conv2d_tok"]

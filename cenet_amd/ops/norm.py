@@ -1,18 +1,13 @@
 """cenet_amd.ops.norm — LayerNorm over the last dimension and train-mode BatchNorm (+ fused activation).
-Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` exposes every name as before)."""
+Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` re-exports the names in `__all__`)."""
 from __future__ import annotations
-
-import contextlib
-import math
-import os
-from typing import Optional, Sequence
 
 import torch
 from torch.autograd import Function
 
 from .. import kern
-from .infra import *  # noqa: F401,F403
-from .linear import *  # noqa: F401,F403
+from .infra import _ZeroWs, _act, _bf, _c, _empty, _grad_pair, _ln_bwd, _wgrad_rows
+from .linear import PatchTokFn, conv2d_tok, patch_rows_conv
 
 
 # =====================================================================================================
@@ -40,9 +35,7 @@ class LayerNormFn(Function):
         Cn = x.shape[-1]
         rows = x.numel() // Cn
         dx = torch.empty_like(x)
-        dg, db = grad_buf(gp), grad_buf(bp)
-        if dg is None:  # frozen affine: accumulate into scratch
-            dg, db = _zeros((Cn,), x), _zeros((Cn,), x)
+        dg, db = _grad_pair(gp, bp, x, (Cn,))
         _ln_bwd(g, x, gamma, mean, rstd, dx, dg, db, rows, Cn, up_scale=ctx.up_scale)
         return dx, None, None, None, None
 
@@ -78,20 +71,9 @@ class LinearLNFn(Function):
         K, N = x.shape[-1], W.shape[0]
         R = x.numel() // K
         d = torch.empty_like(xpre)
-        dg, dbt = grad_buf(gp), grad_buf(btp)
-        if dg is None:
-            dg, dbt = _zeros((N,), xpre), _zeros((N,), xpre)
+        dg, dbt = _grad_pair(gp, btp, xpre, (N,))
         _ln_bwd(g, xpre, gamma, mean, rstd, d, dg, dbt, R, N)
-        dW, db = grad_buf(Wp), grad_buf(bp)
-        if dW is not None and _wgrad_deferrable(N, K, d, x, K=R):
-            _wgrad_defer(d, 0, N, 0, x, 0, K, 0, dW, 0, db, N, K, R, 1, 0)
-        elif dW is not None or db is not None:
-            with _wgrad_side(d, x):
-                if dW is not None:
-                    kern.gemm(kern.mat_plain(d, 1, N, kfast=0), kern.mat_plain(x, K, 1, kfast=0), dW, N, K, R, scr=K, scc=1,
-                              splits=kern.pick_splits(N, K, 1, (R + 31) // 32), atomic=True, asum=db)
-                else:
-                    kern.col_sum(d, db, R, N)
+        _wgrad_rows(d, x, Wp, bp, N, K, R)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
@@ -110,9 +92,8 @@ def sr_conv_ln(x, H, Wd, W, b, stride, gamma, beta, eps):
     """LayerNorm(Conv2d(k = stride, no padding)(tokens as a map)) -> tokens (pvtv2.py:93-95,99-100)"""
     x = _c(x)
     B, N, C = x.shape
-    k = W.shape[2]
-    if (k == stride and W.shape[3] == k and k in (2, 4, 8) and H % k == 0 and Wd % k == 0 and N == H * Wd and W.is_contiguous()):
-        xp = PatchTokFn.apply(x, H, Wd, k)
+    if patch_rows_conv(W, N, H, Wd, stride):
+        xp = PatchTokFn.apply(x, H, Wd, stride)
         if linear_ln_supported(xp, W, b):
             return LinearLNFn.apply(xp, W, b, gamma, beta, eps)
     return layernorm(conv2d_tok(x, H, Wd, W, b, stride=stride, pad=0, out_layout="tok"), gamma, beta, eps)
@@ -150,9 +131,7 @@ class LayerNormResFn(Function):
             return g_res, None, None, None, None
         g = _c(g)
         dx = torch.empty_like(x)
-        dg, db = grad_buf(gp), grad_buf(bp)
-        if dg is None:
-            dg, db = _zeros((Cn,), x), _zeros((Cn,), x)
+        dg, db = _grad_pair(gp, bp, x, (Cn,))
         _ln_bwd(g, x, gamma, mean, rstd, dx, dg, db, rows, Cn, dx_add=_c(g_res), up_scale=ctx.up_scale)
         return dx, None, None, None, None
 
@@ -205,9 +184,7 @@ class BatchNormFn(Function):
         HW = x.numel() // (B * Cn)
         dx = torch.empty_like(x)
         ws = _empty((2 * Cn * 256,), x)  # CENET_BN_WS_FLOATS(C)
-        dg, db = grad_buf(wp), grad_buf(bp)
-        if dg is None:
-            dg, db = _zeros((Cn,), x), _zeros((Cn,), x)
+        dg, db = _grad_pair(wp, bp, x, (Cn,))
         kern.bn_bwd(g, Cn * HW, x, Cn * HW, dx, Cn * HW, mean, var, eps, weight, bias, act, slope, B, Cn, HW, ws, dg, db,
                     dx_add=g_tap)
         return (dx,) + (None,) * 11
@@ -218,4 +195,5 @@ def batchnorm(x, weight, bias, rmean, rvar, nbt, training, eps=1e-5, act="none",
     return BatchNormFn.apply(x, weight, bias, rmean, rvar, nbt, training, eps, act, slope, momentum, tap)
 
 
-__all__ = [n for n in dir() if not n.startswith("__")]
+__all__ = ["LayerNormFn", "LinearLNFn", "linear_ln_supported", "sr_conv_ln", "layernorm", "LayerNormResFn", "layernorm_res", "BatchNormFn",
+           "batchnorm"]

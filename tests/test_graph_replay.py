@@ -88,7 +88,7 @@ def test_replay_trains_like_eager(mode):
 @pytest.mark.parametrize("mode", ["eager", "graph", "segmented"])
 def test_branch_streams_train_alike(mode):
     """ops.set_branch_streams(True): the head's residual block on a second stream beside the decoder, its backward held to x4
-    (ops.BranchGate) — off by default (measured slower under replay, ops.py) but kept correct: same trajectory as the one-stream
+    (ops.BranchGate) — off by default (measured slower under replay, ops/infra.py) but kept correct: same trajectory as the one-stream
     step in eager launches, under one captured graph, and under the segmented captures of the N > 1 path."""
     dev = torch.device("cuda:0")
     old_bf = kern.set_compute_bf16(True)
