@@ -784,9 +784,7 @@ extern "C" int cenet_diffattn_heads_fwd_bf16(const cenet_diffattn_t* p, hipStrea
   } else if (a.hd <= 16) {
     // one 32-query tile per wave; bounded to three workgroups per CU, the kernel takes 122 registers and runs four (two tiles
     // per wave: 198 registers, two workgroups)
-    static const int v = getenv("CENET_DATTN_QT2") ? 2 : 1;
-    if (v == 2 && a.N >= 1024) CENET_LAUNCH((dattn_fwd_kernel<16, 2, 2, false>), dim3(cdiv(a.N, 256), bh), dim3(256), stream, a);
-    else CENET_LAUNCH((dattn_fwd_kernel<16, 1, 3, false>), dim3(cdiv(a.N, 128), bh), dim3(256), stream, a);
+    CENET_LAUNCH((dattn_fwd_kernel<16, 1, 3, false>), dim3(cdiv(a.N, 128), bh), dim3(256), stream, a);
   } else if (a.hd <= 32) {
     CENET_LAUNCH((dattn_fwd_kernel<32, 1, 2, false>), dim3(cdiv(a.N, 128), bh), dim3(256), stream, a);
   } else if (a.hd == 40 && !da_hd40_p64()) {
@@ -1218,11 +1216,9 @@ extern "C" int cenet_sra_attn_fwd_bf16(const bf* q, const bf* kv, bf* o, float* 
   SraFwdArgs a;
   a.q = q; a.kv = kv; a.o = o; a.lse = lse; a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.C = 64 * H; a.scale = scale;
   // two workgroups per CU: ~512 workgroups fill the chip once
-  static const char* e = getenv("CENET_SRA_FWD_TILES");  // measurement aid
   int tiles = 1;
   while (tiles < 8 && (long)cdiv(Nq, 128 * tiles) * B * H > 1024) ++tiles;
-  if (e) tiles = atoi(e);
-  a.tiles = tiles < 1 ? 1 : tiles;
+  a.tiles = tiles;
   CENET_LAUNCH(sra_fwd_kernel, dim3(cdiv(Nq, 128 * a.tiles), B * H), dim3(256), stream, a);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
@@ -1236,11 +1232,9 @@ extern "C" int cenet_sra_attn_bwd_blocks_supported(int hd, int Nk) { return hd =
 // 32-query tiles per wave: the kernel runs one workgroup per CU (484 registers), so more than 256 workgroups is a second
 // round; measured best (B = 32): 4 tiles at 3136 queries (42 us), 2 at 784 / 196 (31 us), 1 at 49 (25 us)
 static int sra_tiles(int B, int H, int Nq) {
-  static const char* e = getenv("CENET_SRA_TILES");
   int tiles = 1;
   while (tiles < 8 && (long)cdiv(Nq, 128 * tiles) * B * H > 256) ++tiles;
-  if (e) tiles = atoi(e);
-  return tiles < 1 ? 1 : tiles;
+  return tiles;
 }
 // 1 when the launch for this problem puts every query of a (batch, head) in ONE workgroup: dK/dV then need no cross-workgroup
 // sum and cenet_sra_attn_bwd_direct_bf16 stores them as bf16 (the 14x14 and 7x7 stages of the ACDC preset)

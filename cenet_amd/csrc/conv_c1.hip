@@ -333,8 +333,7 @@ extern "C" int cenet_conv_c1_fwd_bf16(const bf16_t* x, const float* w, bf16_t* y
   ConvC1Args a;
   a.x = x; a.dy = nullptr; a.w = w; a.y = y; a.dw = nullptr; a.B = B; a.Cout = Cout; a.H = H; a.W = W; a.rows_per_wg = 8;
   const dim3 grid(cdiv(W, 128), cdiv(H, 8), B);
-  static const bool no_mfma = getenv("CENET_C1_NO_MFMA") != nullptr;  // measurement aid
-  if (k == 5 && (W & 15) == 0 && !no_mfma && ((uintptr_t)y & 7) == 0) {
+  if (k == 5 && (W & 15) == 0 && ((uintptr_t)y & 7) == 0) {
     cenet_conv_note("conv_c1_fwd_mfma5_kernel rows_per_wg=8");
     CENET_LAUNCH(conv_c1_fwd_mfma5_kernel, grid, dim3(256), stream, a);
     CENET_CHECK_LAUNCH();
@@ -361,8 +360,7 @@ extern "C" int cenet_conv_c1_wgrad_bf16(const bf16_t* x, const bf16_t* dy, float
   while (rows < H && (long)cdiv(W, 128) * cdiv(H, rows) * B > target) rows += 8;
   a.rows_per_wg = rows;
   const dim3 grid(cdiv(W, 128), cdiv(H, rows), B);
-  static const bool no_mfma = getenv("CENET_C1_NO_MFMA") != nullptr;  // measurement aid
-  if (k == 5 && (W & 31) == 0 && !no_mfma && ((uintptr_t)dy & 15) == 0) {
+  if (k == 5 && (W & 31) == 0 && ((uintptr_t)dy & 15) == 0) {
     cenet_conv_note("conv_c1_wgrad_mfma5_kernel rows_per_wg=%d", rows);
     CENET_LAUNCH(conv_c1_wgrad_mfma5_kernel, grid, dim3(256), stream, a);
     CENET_CHECK_LAUNCH();

@@ -510,11 +510,8 @@ extern "C" int cenet_conv_wgrad_direct_bf16(const bf16_t* x, const bf16_t* dy, f
   if (!cenet_conv_wgrad_direct_supported(Cin, Cout, k, 1, k / 2)) return CENET_EUNSUPPORTED;
   ConvWgradArgs a;
   a.x = x; a.dy = dy; a.ws = ws; a.B = B; a.H = H; a.W = W;
-  {
-    static const bool no_vec = getenv("CENET_WGRAD_NO_VEC") != nullptr;  // measurement aid
-    a.vec = !no_vec && (W & 7) == 0 && ((((uintptr_t)x | (uintptr_t)dy) & 15) == 0) && H < 256 &&
-            (long)(Cin > Cout ? Cin : Cout) * H * W < (1L << 30);  // (row index in 8 bits, image-relative offsets in an int)
-  }
+  a.vec = (W & 7) == 0 && ((((uintptr_t)x | (uintptr_t)dy) & 15) == 0) && H < 256 &&
+          (long)(Cin > Cout ? Cin : Cout) * H * W < (1L << 30);  // (row index in 8 bits, image-relative offsets in an int)
   const int th = (k == 5) ? 8 : 4;
   a.tiles_x = cdiv(W, 32);
   a.tiles_y = cdiv(H, th);

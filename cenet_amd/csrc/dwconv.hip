@@ -738,8 +738,7 @@ template <typename T>
 static int dwconv3x3_nchw_impl(const T* x, long sxb, const float* w, const float* bias, T* y, long syb, T* a, long sab, int B,
                                int C, int H, int W, int dil, int flip, int act, float slope, hipStream_t stream) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || dil <= 0 || (!y && !a)) return CENET_EINVAL;
-  static const bool plane_off = getenv("CENET_DW_NO_PLANE") != nullptr;
-  if (sizeof(T) == 2 && !plane_off && ((sxb | syb | sab) & 3) == 0 && quad_aligned<T>(x) && (!y || quad_aligned<T>(y)) &&
+  if (sizeof(T) == 2 && ((sxb | syb | sab) & 3) == 0 && quad_aligned<T>(x) && (!y || quad_aligned<T>(y)) &&
       (!a || quad_aligned<T>(a)) && ((long)H * W) % 4 == 0) {
     const int ppw = dwp_ppw(B * C, H, W, dil);
     if (ppw > 0) {
@@ -1183,8 +1182,7 @@ static int dw_tile_launch(DwTileArgs a, int B, hipStream_t stream) {
     else                                                                                                         \
       CENET_LAUNCH((dw3x3_tok_tile_kernel<TH_, TW_, MODE, -1>), grid, dim3(256), stream, a);                     \
   }
-  static const bool plane_off = getenv("CENET_DW_NO_PLANE") != nullptr;  // measurement aid
-  if (!plane_off && a.H == a.W && (a.H == 14 || a.H == 7) && (a.C & 63) == 0 && B <= 65535) {
+  if (a.H == a.W && (a.H == 14 || a.H == 7) && (a.C & 63) == 0 && B <= 65535) {
     if (a.H == 14) dw_plane_go<14, MODE>(a, B, stream);
     else dw_plane_go<7, MODE>(a, B, stream);
     CENET_CHECK_LAUNCH();
@@ -1352,8 +1350,7 @@ template <typename T>
 static int dwconv3x3_wgrad_nchw_acc_impl(const T* x, long sxb, const T* dy, long sgb, float* dw_acc, float* dbias_acc, int B,
                                          int C, int H, int W, int dil, hipStream_t stream) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return CENET_EINVAL;
-  static const bool plane_off = getenv("CENET_DW_NO_PLANE") != nullptr;
-  if (sizeof(T) == 2 && !plane_off && ((sxb | sgb) & 3) == 0 && quad_aligned<T>(x) && quad_aligned<T>(dy)) {
+  if (sizeof(T) == 2 && ((sxb | sgb) & 3) == 0 && quad_aligned<T>(x) && quad_aligned<T>(dy)) {
     const int ppw = dwp_ppw(B * C, H, W, dil);
     if (ppw > 0) {
       DwPlaneArgs p;
@@ -1362,9 +1359,8 @@ static int dwconv3x3_wgrad_nchw_acc_impl(const T* x, long sxb, const T* dy, long
       p.BC = B * C; p.C = C; p.H = H; p.W = W; p.dil = dil; p.flip = 0; p.act = 0; p.ppw = ppw; p.slope = 0.f;
       // one channel across a group of images per workgroup where a plane is at most 1024 quads of whole rows and the batch is deep
       // enough to share a workgroup: ~1 000 - 2 000 workgroups
-      static const bool chan_off = getenv("CENET_DW_WGRAD_NO_CHAN") != nullptr;  // measurement aid
       const int nq = (H * W) >> 2, ps = (H + 2 * dil) * (W + 2 * dil);
-      if (!chan_off && (W & 3) == 0 && nq <= 1024 && B >= 4 && C <= 65535) {
+      if ((W & 3) == 0 && nq <= 1024 && B >= 4 && C <= 65535) {
         int np = 1024 / nq;
         if (np > DWP_MAX / ps) np = DWP_MAX / ps;
         if (np > B) np = B;

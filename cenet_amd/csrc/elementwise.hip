@@ -1339,8 +1339,7 @@ static int col_sum_acc_impl(const T* a, float* out_acc, long R, int C, hipStream
     const int quads = C / 4;
     const int tpr = quads >= 64 ? 64 : (quads >= 32 ? 32 : 16);
     const int ctiles = cdiv(quads, tpr);
-    static const int wg_small = getenv("CENET_COLSUM_WGS") ? atoi(getenv("CENET_COLSUM_WGS")) : 256;  // measurement aid
-    const long target = C <= 128 ? wg_small : 2048;
+    const long target = C <= 128 ? 256 : 2048;
     long rpb = (R * ctiles + target - 1) / target;
     if (rpb < 64) rpb = 64;
     rpb = (rpb + 15) & ~15L;

@@ -146,9 +146,8 @@ static int gemm_dispatch(const cenet_mat_t* A, const cenet_mat_t* B, const cenet
     g.cvec = E->scr == 1 && m4(E->scc) && m4(E->scb) && m4(E->scb2) && alq(E->C) &&
              (!E->R || (E->srr == 1 && m4(E->src) && m4(E->srb) && m4(E->srb2) && alq(E->R)));
   {
-    static const bool no_stage = getenv("CENET_GEMM_NO_STAGE") != nullptr;  // measurement aid
     const long so = swap ? E->scr : E->scc;
-    g.cvec8 = !no_stage && bf && g.cvec && (so % 8) == 0 && (E->scb % 8) == 0 && (E->scb2 % 8) == 0 && (((uintptr_t)E->C & 15) == 0);
+    g.cvec8 = bf && g.cvec && (so % 8) == 0 && (E->scb % 8) == 0 && (E->scb2 % 8) == 0 && (((uintptr_t)E->C & 15) == 0);
   }
   int bm, bn;
   pick_tile(M, N, nbatch, splits, &bm, &bn);
@@ -181,8 +180,7 @@ static int gemm_dispatch(const cenet_mat_t* A, const cenet_mat_t* B, const cenet
       akf = bkf = -1;
     }
   }
-  static const bool ring_off = getenv("CENET_GEMM_NO_RING") != nullptr;
-  const bool ring = !ring_off && akf >= 0 && bkf >= 0 && !E->cmode && E->act == ACT_NONE && M >= 48 && N >= 48;
+  const bool ring = akf >= 0 && bkf >= 0 && !E->cmode && E->act == ACT_NONE && M >= 48 && N >= 48;
   if (ring) {
     // tile choice, from a sweep of every GEMM shape of a training step over the four tiles (tools/gemm_sweep.sh): the
     // 64x64 tile with its 4-stage ring wins wherever the reduction is long (the step's contractions are latency-bound:
@@ -207,8 +205,6 @@ static int gemm_dispatch(const cenet_mat_t* A, const cenet_mat_t* B, const cenet
       auto wgs = [&](int a, int b) { return (long)cdiv(M, a) * cdiv(N, b) * nbatch; };
       if (wgs(bm, bn) < want && bm == 128 && bn == 128) (M >= N ? bm : bn) = 64;
       if (wgs(bm, bn) < want && (bm == 128 || bn == 128)) bm = bn = 64;
-      static const char* fb = getenv("CENET_RING_TILE_BATCHED");  // measurement aid: per-image (nbatch >= 8) launches only
-      if (fb && nbatch >= 8) sscanf(fb, "%dx%d", &bm, &bn);
     }
   }
   const int kstep = ring ? 64 : BK;
@@ -239,8 +235,7 @@ static int gemm_dispatch(const cenet_mat_t* A, const cenet_mat_t* B, const cenet
   const bool im = B->mode != 0;
   int rc;
   // one or two K-steps, nothing to pipeline inside a tile: persistent workgroups with the ring over TILES (gemm_ring.h)
-  static const bool stream_off = getenv("CENET_GEMM_NO_STREAM") != nullptr;
-  const bool rstream = ring && !stream_off && !E->atomic && nkb == 1 && splits <= 1 && !g.ring_unal && (K == 64 || K == 128) &&
+  const bool rstream = ring && !E->atomic && nkb == 1 && splits <= 1 && !g.ring_unal && (K == 64 || K == 128) &&
                        (long)cdiv(M, 64) * cdiv(N, 64) * nbatch >= 768;
   if (rstream) {
     snprintf(g_last_kernel, sizeof g_last_kernel, "gemm_ring_stream_kernel<%s, %s, %s, %d>", tf(akf), tf(bkf), tf(swap), K / 64);

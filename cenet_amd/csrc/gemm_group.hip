@@ -338,12 +338,7 @@ static long grp_env(const char* name, long dflt) {
 // outputs with both sides >= 128 (stages 2 - 4, the DSEB projections, the upper decoder levels) run fastest on 128x128 tiles
 // with a 2-stage ring (half the operand bytes through LDS per FLOP: 234 vs 381 us for stage 2, 297 vs 477 us for stage 3);
 // skinny outputs (stage 1: 64 .. 512 x 64) keep the 64x64 tile with its 4-stage ring (304 vs 385 us).
-static GrpTile grp_tile(int cls) {
-  GrpTile t = cls ? GrpTile{128, 128, 2} : GrpTile{64, 64, 4};
-  const char* v = getenv("CENET_GROUP_TILE");  // "128x128x2" etc. for every problem: measurement aid
-  if (v) sscanf(v, "%dx%dx%d", &t.bm, &t.bn, &t.ns);
-  return t;
-}
+static GrpTile grp_tile(int cls) { return cls ? GrpTile{128, 128, 2} : GrpTile{64, 64, 4}; }
 static int grp_class(const cenet_wgrad_prob_t& q) { return (q.M >= 128 && q.N >= 128) ? 1 : 0; }
 // One launch = up to GRP_MAXP problems of one orientation and one tile class.  Every item should reduce about `depth` K-steps:
 // deep enough to amortise the ring's fill and the epilogue, shallow enough that the launch has a few items per workgroup slot.
@@ -402,9 +397,6 @@ template <bool KF>
 static int grp_launch_tile(const GroupArgs& ga, GrpTile t, float* ws, int items, int folds, int phase, hipStream_t stream) {
   if (t.bm == 64 && t.bn == 64 && t.ns == 4) grp_launch<KF, 64, 64, 4>(ga, ws, items, folds, phase, stream);
   else if (t.bm == 128 && t.bn == 128 && t.ns == 2) grp_launch<KF, 128, 128, 2>(ga, ws, items, folds, phase, stream);
-  else if (t.bm == 128 && t.bn == 128 && t.ns == 3) grp_launch<KF, 128, 128, 3>(ga, ws, items, folds, phase, stream);
-  else if (t.bm == 128 && t.bn == 64 && t.ns == 3) grp_launch<KF, 128, 64, 3>(ga, ws, items, folds, phase, stream);
-  else if (t.bm == 64 && t.bn == 128 && t.ns == 3) grp_launch<KF, 64, 128, 3>(ga, ws, items, folds, phase, stream);
   else return CENET_EUNSUPPORTED;
   return CENET_OK;
 }

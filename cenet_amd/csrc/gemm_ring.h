@@ -502,8 +502,7 @@ static int launch_ring_stream(const GemmArgs& g, int nbatch, hipStream_t stream)
   const int tx = cdiv(g.N, 64), ty = cdiv(g.M, 64);
   const long total = (long)tx * ty * nbatch;
   if (total > (1L << 30)) return CENET_EUNSUPPORTED;
-  static const char* ge = getenv("CENET_STREAM_WGS");  // measurement aid
-  long wgs = ge ? atol(ge) : 1024;  // (measured on the whole step: 256 / 512 / 768 / 1024 / 2048 -> 21.6 / 21.55 / 21.50 / 21.46 / 21.47 ms)
+  long wgs = 1024;  // (measured on the whole step: 256 / 512 / 768 / 1024 / 2048 -> 21.6 / 21.55 / 21.50 / 21.46 / 21.47 ms)
   if (wgs > total) wgs = total;
   if (wgs >= 8) wgs &= ~7L;
   if (g.K == 64) CENET_LAUNCH((gemm_ring_stream_kernel<AKF, BKF, SWAP, 1>), dim3((unsigned)wgs), dim3(256), stream, g, tx, ty, (int)total);

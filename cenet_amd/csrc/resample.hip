@@ -533,7 +533,7 @@ static int bilinear_bwd_impl(const T* dy, long sgb, T* dx, long sdb, int B, int 
     CENET_CHECK_LAUNCH();
     return CENET_OK;
   }
-  if (sizeof(T) == 2 && Hi <= 8 && Wi <= 8 && Ho <= 64 && Wo <= 64 && scale_h > 1e-6f && scale_w > 1e-6f && !getenv("CENET_BIL_NO_SEP")) {
+  if (sizeof(T) == 2 && Hi <= 8 && Wi <= 8 && Ho <= 64 && Wo <= 64 && scale_h > 1e-6f && scale_w > 1e-6f) {
     CENET_LAUNCH((bilinear_bwd_sep_kernel<T>), dim3(B * C), dim3(256), stream, dy, sgb, dx, sdb, C, Hi, Wi, Ho, Wo, scale_h, scale_w,
                  align_corners);
     CENET_CHECK_LAUNCH();
@@ -547,7 +547,7 @@ static int bilinear_bwd_impl(const T* dy, long sgb, T* dx, long sdb, int B, int 
     return CENET_OK;
   }
   if (sizeof(T) == 2 && align_corners && Ho == 2 * Hi && Wo == 2 * Wi && (Wi & 3) == 0 && Hi >= 4 && Wi >= 4 &&
-      ((((uintptr_t)dy | (uintptr_t)dx) & 7) == 0) && ((sgb | sdb) & 3) == 0 && !getenv("CENET_BIL_NO_UP2AC")) {
+      ((((uintptr_t)dy | (uintptr_t)dx) & 7) == 0) && ((sgb | sdb) & 3) == 0) {
     CENET_LAUNCH((bilinear_up2ac_bwd_kernel<T>), dim3(B * C, chunks_one(Hi * Wi / 4)), dim3(256), stream, dy, sgb, dx, sdb, C, Hi, Wi,
                  scale_h, scale_w);
     CENET_CHECK_LAUNCH();

@@ -751,11 +751,10 @@ extern "C" int cenet_srm_conv_fwd_f32(const float* u, const float* pwc, const fl
 extern "C" int cenet_srm_conv_bwd_acc_f32(const float* u, const float* df, const float* pwc, const float* dwc, float* du,
                                           float* dpwc_acc, float* ddwc_acc, int B, int H, int W, hipStream_t stream) {
   if (B <= 0 || H <= 0 || W <= 0) return CENET_EINVAL;
-  static const int gx = getenv("CENET_SRM_BWD_GX") ? atoi(getenv("CENET_SRM_BWD_GX")) : 0;  // measurement aid
-  // measured at the four decoder levels of the ACDC preset, average us per call: gx = 1: 52, 2: 32, 4: 23, 8: 19, 12: 21, 16: 21, 32: 29
+  // measured at the four decoder levels of the ACDC preset, average us per call, by grid.x: 1: 52, 2: 32, 4: 23, 8: 19, 12: 21, 16: 21, 32: 29
   int want = cdiv(H * W, 256);
   if (want > 8) want = 8;
-  CENET_LAUNCH(srm_conv_bwd_kernel, dim3(gx > 0 ? gx : want, B), dim3(256), stream, u, df, pwc, dwc, du, dpwc_acc, ddwc_acc, H, W);
+  CENET_LAUNCH(srm_conv_bwd_kernel, dim3(want, B), dim3(256), stream, u, df, pwc, dwc, du, dpwc_acc, ddwc_acc, H, W);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
 }

@@ -14,7 +14,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from typing import Optional
 
 import torch
@@ -495,7 +494,7 @@ def res_tail_img_bwd(g, x2, img, mean2, var2, g2, b2, eps2, imean, ivar, w3, g3,
 
 # ---- depthwise conv ------------------------------------------------------------------------------------
 # ---- channel-local fused chains (csrc/chanloc.hip) --------------------------------------------------------------------------
-_NO_CHANLOC = os.environ.get("CENET_NO_CHANLOC") is not None  # measurement aid: the unfused launch chains
+_NO_CHANLOC = False  # True: the unfused launch chains (the tests' reference for the fused kernels)
 
 
 def eucb_supported(x) -> bool:
@@ -590,10 +589,6 @@ def dw_nchw(x, sxb, w, bias, y, syb, a, sab, B, Cn, H, W, dil, flip, act="none",
           B, Cn, H, W, dil, flip, ACT[act], slope)
 
 
-
-_NO_DW_MULTI = os.environ.get("CENET_DW_NO_MULTI") is not None  # measurement aid: the branches one launch each
-
-
 def _ptr_arr(vals):
     return (C.c_void_p * len(vals))(*vals)
 
@@ -603,7 +598,7 @@ def dw_nchw_multi(branches, B, H, W, flip):
     of bf16 NCHW channel slices in ONE launch.  Returns False when the library has no single-launch form for them (the caller
     then launches them one by one)."""
     n = len(branches)
-    if n < 1 or n > 4 or _NO_DW_MULTI or any(not is_bf16(b[0]) or not is_bf16(b[4]) for b in branches):
+    if n < 1 or n > 4 or any(not is_bf16(b[0]) or not is_bf16(b[4]) for b in branches):
         return False
     _chk(*[b[0] for b in branches], *[b[3] for b in branches], *[b[4] for b in branches])
     xs = _ptr_arr([b[0].data_ptr() + 2 * b[1] for b in branches])
@@ -624,7 +619,7 @@ def dw_wgrad_nchw_multi(branches, B, H, W):
     """branches: [(x, x_off, sxb, dy, g_off, sgb, dw, C, dil)]: dw[i] += dy[i] (*) x[i] for up to 4 branches in ONE launch; False
     when unsupported"""
     n = len(branches)
-    if n < 1 or n > 4 or _NO_DW_MULTI or any(not is_bf16(b[0]) or not is_bf16(b[3]) for b in branches):
+    if n < 1 or n > 4 or any(not is_bf16(b[0]) or not is_bf16(b[3]) for b in branches):
         return False
     _chk(*[b[0] for b in branches], *[b[3] for b in branches], *[b[6] for b in branches])
     xs = _ptr_arr([b[0].data_ptr() + 2 * b[1] for b in branches])
@@ -654,7 +649,6 @@ def dw_tok_tiled(x):
     return is_bf16(x) and x.shape[-1] % 8 == 0 and x.data_ptr() % 16 == 0
 
 
-
 def pvt_mlp_supported(x, Cn, HD, H, W) -> bool:
     """the fused PVT-MLP kernels (pvt_mlp.hip) have an instance for these bf16 tokens"""
     return bool(is_bf16(x) and x.data_ptr() % 16 == 0 and _lib.lib().cenet_pvt_mlp_supported(Cn, HD, H, W))
@@ -667,7 +661,6 @@ def pvt_mlp_fwd(x, ln_g, ln_b, eps, w1, b1, wd, bd, w2, b2, bscale, y, B, H, W, 
     xn, mean, rstd, h, a = saved if saved is not None else (None,) * 5
     _call("cenet_pvt_mlp_fwd_bf16", x, ln_g, ln_b, eps, w1, b1, wd, bd, w2, b2, bscale, y, xn, mean, rstd, h, a, B, H, W,
           Cn, HD)
-
 
 
 def pvt_mlp_bwd(g, bscale, w1, w2, wd, bd, h, x, ln_g, mean, rstd, gu, dh, dx, dwd, dbd, dln_g, dln_b, db2, B, H, W, Cn, HD,
@@ -758,11 +751,8 @@ def srm_conv_bwd(u, df, pwc, dwc, du, dpwc, ddwc, B, H, W):
     _call("cenet_srm_conv_bwd_acc_f32", u, df, pwc, dwc, du, dpwc, ddwc, B, H, W)
 
 
-_NO_SRM_FUSED = os.environ.get("CENET_NO_SRM_FUSED") is not None  # measurement aid
-
-
 def srm_fused_supported(B, H, W) -> bool:
-    return (not _NO_CHANLOC) and (not _NO_SRM_FUSED) and bool(_lib.lib().cenet_srm_fused_supported(B, H, W))
+    return (not _NO_CHANLOC) and bool(_lib.lib().cenet_srm_fused_supported(B, H, W))
 
 
 def srm_parts(B, H, W) -> int:

@@ -31,18 +31,11 @@ class OutHead(nn.Module):
 
     def branch(self, x):
         """w * MaxPool2(ResBlock5x5(x)) (out.py:69): block tail and pool fused (UnetResBlock.forward).  Depends on the input image
-        only — CENet._forward launches it on a branch stream ahead of the encoder and hands the result to forward(rb=...)"""
+        only"""
         return self.rb[0](x, self.w)
 
-    def forward(self, dec, x, rb=None):
-        if rb is None:
-            rb = self.branch(x)
-        elif rb.is_cuda:
-            cur = torch.cuda.current_stream(rb.device)
-            bs = ops.branch_stream(rb)
-            if bs is not None:
-                cur.wait_stream(bs)
-                rb.record_stream(cur)
+    def forward(self, dec, x):
+        rb = self.branch(x)
         d = self.up(dec)
         z = ops.concat2(d, rb)
         y = self.out[1](self.out[0](z))

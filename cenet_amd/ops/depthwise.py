@@ -2,8 +2,6 @@
 Part of the cenet_amd.ops package (split by operator family in round 6; `from cenet_amd import ops` re-exports the names in `__all__`)."""
 from __future__ import annotations
 
-import os
-
 import torch
 from torch.autograd import Function
 
@@ -120,7 +118,7 @@ class PvtMlpFn(Function):
 
 
 def pvt_mlp_supported(x, HD, H, Wd) -> bool:
-    return x.dim() == 3 and kern.pvt_mlp_supported(x, x.shape[-1], HD, H, Wd) and os.environ.get("CENET_PVT_MLP_FUSED", "1") != "0"
+    return x.dim() == 3 and kern.pvt_mlp_supported(x, x.shape[-1], HD, H, Wd)
 
 
 def pvt_mlp(x, H, Wd, ln_g, ln_b, eps, w1, b1, wd, bd, w2, b2, bscale=None):

@@ -1,5 +1,5 @@
 """cenet_amd.ops.infra — shared plumbing of the operator modules: tensor allocation helpers, zero-at-rest workspaces, parameter / gradient views into the
-ParamArena (merged_param), the recorded weight-gradient queue and its per-device state, branch streams, pre-scaled gradient hand-over.
+ParamArena (merged_param), the recorded weight-gradient queue and its per-device state, pre-scaled gradient hand-over.
 
 (ops package overview) Autograd operators of the CENet hot path, forward AND backward on hand-written HIP kernels.
 
@@ -57,19 +57,23 @@ class _ZeroWs:
     front of every use (the dK / dV accumulator of the spatial-reduction attention backward: 7 fills per step).
     A buffer that is taken stays IN USE until give_back_as: a second taker of the same size gets a buffer of its own (up to
     `MAX_LIVE` per size; beyond that the oldest is taken to be the leftover of a pass that raised between the two launches and is
-    filled again).  Single-stream contract: take -> kernel -> give_back_as run on ONE stream (the buffers carry no events); with
-    branch streams enabled the key holds the stream, so the branch streams of branch_stream() each own their buffers."""
-    bufs: dict = {}  # key -> [[tensor, in_use], ...]
+    filled again).  Single-stream contract: take -> kernel -> give_back_as / release run on ONE stream (the buffers carry no
+    events).  Each entry remembers the stream it was taken on and handing it back from another stream raises; the check compares
+    stream ids on the host and orders nothing.  Bodies of _wgrad_side run on the weight-gradient stream and must not use _ZeroWs."""
+    bufs: dict = {}  # (device type, index, element count) -> [[tensor, in_use, stream id of the take], ...]
     MAX_LIVE = 4
 
     @staticmethod
     def _key(dev, n):
-        # the stream is part of the key only while branch streams are on (two streams really do run take -> kernel -> give_back
-        # concurrently then).  Otherwise ONE set per device: GraphedStep warms up on a side stream and torch.cuda.graph captures on
-        # another, and a per-stream key made the capture allocate fresh buffers inside the graph's pool with their zero-fill
-        # captured as a node that re-ran on every replay — the launches this class exists to avoid (ADVICE r5)
-        sid = torch.cuda.current_stream(dev).stream_id if (dev.type == "cuda" and _BRANCH_ON[0]) else 0
-        return (dev.type, dev.index, n, sid)
+        # ONE set per device, whatever the stream: GraphedStep warms up on a side stream and torch.cuda.graph captures on another,
+        # and a per-stream key made the capture allocate fresh buffers inside the graph's pool with their zero-fill captured as a
+        # node that re-ran on every replay — the launches this class exists to avoid (ADVICE r5)
+        return (dev.type, dev.index, n)
+
+    @staticmethod
+    def _sid(dev):
+        """id of dev's current stream; None where no stream is checked (CPU tensors, the host checker)"""
+        return torch.cuda.current_stream(dev).stream_id if dev.type == "cuda" and not kern._lib.is_hostsim() else None
 
     @staticmethod
     def take(shape, ref: Tensor) -> Tensor:
@@ -80,30 +84,42 @@ class _ZeroWs:
         e = next((e for e in es if not e[1]), None)
         if e is None:
             if len(es) < _ZeroWs.MAX_LIVE:
-                e = [kern.zero_(torch.empty(n, device=ref.device, dtype=torch.float32)), False]
+                e = [kern.zero_(torch.empty(n, device=ref.device, dtype=torch.float32)), False, None]
                 es.append(e)
             else:  # every buffer of this size is marked in use: leftovers of passes that raised
                 e = es.pop(0)
                 es.append(e)
                 kern.zero_(e[0])
-        e[1] = True
+        e[1], e[2] = True, _ZeroWs._sid(ref.device)
         return e[0].view(shape)
+
+    @staticmethod
+    def _entry(ws: Tensor):
+        """the entry of ws, checked to come back on the stream that took it; None for a tensor that is not one of the buffers"""
+        for e in _ZeroWs.bufs.get(_ZeroWs._key(ws.device, ws.numel()), ()):
+            if e[0].data_ptr() == ws.data_ptr():
+                sid = _ZeroWs._sid(ws.device)
+                if e[1] and sid != e[2]:
+                    raise RuntimeError(f"_ZeroWs: buffer taken on stream {e[2]} is handed back on stream {sid}; take -> kernel -> "
+                                       "give_back_as must run on one stream")
+                return e
+        return None
 
     @staticmethod
     def release(ws: Tensor):
         """ws is zero again (a kernel of the caller cleared it)"""
-        for e in _ZeroWs.bufs.get(_ZeroWs._key(ws.device, ws.numel()), ()):
-            if e[0].data_ptr() == ws.data_ptr():
-                e[1] = False
+        e = _ZeroWs._entry(ws)
+        if e is not None:
+            e[1] = False
 
     @staticmethod
     def give_back_as(ws: Tensor, like: Tensor, bias: Optional[Tensor] = None) -> Tensor:
         """-> a tensor of like's dtype (bf16) holding ws (+ bias over the last axis); ws is zero again"""
+        e = _ZeroWs._entry(ws)
         out = torch.empty(ws.shape, device=ws.device, dtype=like.dtype)
         kern.cast_clear(ws, out, bias)
-        for e in _ZeroWs.bufs.get(_ZeroWs._key(ws.device, ws.numel()), ()):
-            if e[0].data_ptr() == ws.data_ptr():
-                e[1] = False
+        if e is not None:
+            e[1] = False
         return out
 
 
@@ -177,14 +193,10 @@ def merged_buffer(bs):
 class _WgradCfg:
     """process-wide SWITCHES of the weight-gradient machinery (configuration, not per-pass state)"""
     overlap = False  # weight-gradient kernels on a second HIP stream (set_wgrad_overlap)
-    grouping = os.environ.get("CENET_WGRAD_GROUP", "1") != "0"  # record + one grouped launch (0: the per-layer launches of round 2)
+    grouping = True  # record + one grouped launch (set_wgrad_grouping(False): the per-layer launches of round 2)
     hold_bytes = int(float(os.environ.get("CENET_WGRAD_HOLD_MB", "3072")) * (1 << 20))  # recorded operands kept alive at most
     hold = False  # measurement aid (wgrad_hold): no automatic flush, the caller flushes
-    prescale = os.environ.get("CENET_LN_PRESCALE", "1") != "0"  # LayerNorm backward also writes the DropPath-scaled gradient
-    # the GROUPED launches of a flush on the weight-gradient stream (round 5): ten chip-filling launches per step that only the
-    # optimizer waits for, beside a backward chain of small latency-bound kernels — unlike the ~150 per-layer launches of round 2
-    # (whose fork / join edges cost more under replay than the overlap bought) this is five forks per step
-    flush_side = os.environ.get("CENET_WGRAD_FLUSH_SIDE", "0") != "0"
+    prescale = True  # LayerNorm backward also writes the DropPath-scaled gradient (False: the tests' reference, one scale pass more)
 
 
 class _WgradState:
@@ -205,7 +217,6 @@ class _WgradState:
         self.held = 0      # their bytes
         self.task = None   # autograd graph task whose end-of-backward callback is queued
         self.ln_items = []  # (partial buffer, dgamma, dbeta) of LayerNorm backward launches: folded by ONE launch at the flush
-        self.rec_streams = []  # the streams the recorded operands were produced on (branch_stream(): more than one)
         # --- the weight-gradient stream
         self.stream = None
         self.events = None
@@ -223,42 +234,14 @@ class _WgradState:
         items, self.items = self.items, []
         ln, self.ln_items = self.ln_items, []
         self.held = 0
-        if self.rec_streams:
-            # operands recorded from a branch stream: the flushing stream is ordered after that stream, and the allocator is told
-            # that the operands are read here as well
-            cur = torch.cuda.current_stream(self.device)
-            other = [r for r in self.rec_streams if r != cur]
-            self.rec_streams = []
-            for r in other:
-                cur.wait_stream(r)
-            if other:
-                for pair in self.keep:
-                    for t in pair:
-                        t.record_stream(cur)
-                for part, _, _ in ln:
-                    part.record_stream(cur)
 
         def go():
             if ln:
                 kern.ln_fold_group(ln)
             if items:
                 kern.wgrad_group(items, self.device)
-        side = _WgradCfg.flush_side and self.device.type == "cuda" and not kern._lib.is_hostsim()
         try:
-            if side:
-                cur = torch.cuda.current_stream(self.device)
-                if self.stream is None:
-                    self.stream = torch.cuda.Stream(self.device)
-                    self.events = [torch.cuda.Event() for _ in range(64)]
-                ev = self.events[self.next_event & 63]
-                self.next_event += 1
-                ev.record(cur)
-                self.stream.wait_event(ev)
-                with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
-                    go()
-                self.side_keep.extend(self.keep)  # (operands stay alive until wgrad_join: the side stream still reads them)
-                self.pending = True
-            elif self.device.type == "cuda" and torch.cuda.current_device() != self.device.index:
+            if self.device.type == "cuda" and torch.cuda.current_device() != self.device.index:
                 with torch.cuda.device(self.device):
                     go()
             else:
@@ -268,75 +251,6 @@ class _WgradState:
 
 
 _WG = {}
-
-# ---- branch streams: independent sub-graphs of the network on a second HIP stream -------------------------------------------
-# The out head's 5x5 residual block reads only the input image (out.py:69): it can run on branch stream 0 beside the decoder, whose
-# small-map kernels leave most of the chip idle; autograd runs each backward node on its forward's stream, so the block's backward
-# (weight gradients only: the image needs no gradient) overlaps the rest of the backward pass the same way (BranchGate chooses
-# where).  Under hipGraph capture the fork / join become graph edges.
-# OFF by default — measured, round 5, same box, ACDC step under hipGraph replay: 18.72 / 18.78 ms without, 19.00 / 19.00 ms with
-# the branch beside the decoder (backward held to x4 or not), 19.01 ms with it beside encoder stage 1.  The replayed graph then
-# spreads its nodes over two hardware queues (486 / 372 kernels in the trace) and pays a cross-queue dependency at every hand-over;
-# that costs more than the ~0.9 ms of residual-block work hidden.  set_branch_streams(True) / CENET_BRANCH_STREAMS=1 turn it on.
-_BRANCH: dict = {}
-_BRANCH_ON = [os.environ.get("CENET_BRANCH_STREAMS") is not None]
-
-
-def set_branch_streams(on: bool) -> bool:
-    old, _BRANCH_ON[0] = _BRANCH_ON[0], bool(on)
-    return old
-
-
-def branch_stream(ref: Tensor, i: int = 0):
-    """branch stream i of ref's device, or None where there are no streams (CPU tensors, the host checker) or it is disabled"""
-    if not _BRANCH_ON[0] or not ref.is_cuda or kern._lib.is_hostsim():
-        return None
-    key = (ref.device.index, i)
-    st = _BRANCH.get(key)
-    if st is None:
-        st = _BRANCH[key] = torch.cuda.Stream(ref.device)
-    return st
-
-
-def branch_gate_enabled() -> bool:
-    return os.environ.get("CENET_BRANCH_GATE", "1") != "0"
-
-
-class _HoldFn(Function):
-    @staticmethod
-    def forward(ctx, t, gate):
-        ctx.gate = gate
-        return t.view_as(t)
-
-    @staticmethod
-    def backward(ctx, g):
-        ev = ctx.gate.event
-        if ev is not None and g.is_cuda:
-            torch.cuda.current_stream(g.device).wait_event(ev)  # (this node runs on its forward's stream: the branch stream)
-        return g, None
-
-
-class BranchGate:
-    """Holds the BACKWARD of a branch-stream sub-graph until some other point of the backward pass has been reached:
-    `y = gate.hold(y)` at the end of the branch (on the branch stream), `t.register_hook(gate.release)` on the tensor whose
-    gradient marks that point.  Without the release the hold does nothing."""
-
-    def __init__(self):
-        self.event = None
-
-    def hold(self, t: Tensor) -> Tensor:
-        return _HoldFn.apply(t, self)
-
-    def release(self, grad):
-        if grad.is_cuda:
-            self.event = torch.cuda.Event()
-            self.event.record(torch.cuda.current_stream(grad.device))
-        return None
-
-
-def branch_streams(device) -> list:
-    """the branch streams created so far on `device` (GradReducer orders the collective after them)"""
-    return [s for (d, _), s in _BRANCH.items() if d == device.index]
 
 
 def _wg(device) -> _WgradState:
@@ -476,10 +390,6 @@ def _wgrad_defer(A: Tensor, a_off: int, lda: int, skbA: int, B: Tensor, b_off: i
 def _defer_begin(st) -> int:
     """before a record: the current autograd graph task; drops the records of a pass that never reached its end"""
     tid = _graph_task_id() if _graph_task_id is not None else 0
-    if st.device.type == "cuda" and _BRANCH:
-        cur = torch.cuda.current_stream(st.device)
-        if cur not in st.rec_streams:
-            st.rec_streams.append(cur)
     if not _WgradCfg.hold and (st.items or st.ln_items) and st.task is not None and tid != st.task:
         # records of a backward pass that never reached its end (it raised: the engine runs no callbacks then).  Their
         # gradients are void; adding them into a later pass's would be wrong, and they must not block that pass's own callback.
@@ -627,8 +537,7 @@ def batch1_semantics(on: bool = True):
         _Batch1.on = old
 
 
-__all__ = ["grad_buf", "merged_param", "refresh_member_shadows", "merged_buffer", "set_branch_streams", "branch_stream",
-           "branch_gate_enabled", "BranchGate", "branch_streams", "set_wgrad_overlap", "wgrad_stream", "wgrad_join", "set_wgrad_grouping",
+__all__ = ["grad_buf", "merged_param", "refresh_member_shadows", "merged_buffer", "set_wgrad_overlap", "wgrad_stream", "wgrad_join", "set_wgrad_grouping",
            "wgrad_hold", "wgrad_pending", "tag_bscale", "wgrad_flush", "bn_momentum", "batch1_semantics", "_empty", "_act", "_bf", "_acc32",
            "_zeros", "_ZeroWs", "_WgradCfg", "_WgradState", "_WG", "_wgrad_side", "_wgrad_deferrable", "_wgrad_rows", "_wgrad_defer", "_ln_bwd",
            "_prescaled_put", "_prescaled_take", "_c", "_gb", "_grad_pair", "_mom", "_Batch1"]

@@ -5,7 +5,7 @@ import torch
 import torch.nn.functional as F
 
 from backend import dev  # noqa: F401
-from cenet_amd import kern
+from cenet_amd import kern, ops
 
 
 # C = 50 exercises the scalar fallback; 320 and 512 the two-pass form; rows not a multiple of the workgroup step
@@ -280,3 +280,33 @@ def test_dpp_wave_reductions(dev):
     assert torch.equal(maxs.cpu(), x.max(1).values.repeat(2))
     want = ((x * 1024.0).to(torch.int32) + torch.arange(64, dtype=torch.int32)).min(1).values
     assert torch.equal(mins.cpu(), want.repeat(2))
+
+
+@pytest.mark.gpu
+def test_zero_ws_comes_back_on_the_stream_that_took_it():
+    """ops._ZeroWs carries no events: take -> kernel -> give_back_as / release on ONE stream, and a hand-back from another stream
+    raises before anything is launched (a host comparison of stream ids, nothing is ordered)"""
+    dv = torch.device("cuda:0")
+    like = torch.empty(1, device=dv, dtype=torch.bfloat16)
+    key = ops._ZeroWs._key(dv, 64)
+    ops._ZeroWs.bufs.pop(key, None)
+    other = torch.cuda.Stream(dv)
+    cur = torch.cuda.current_stream(dv).stream_id
+    assert other.stream_id != cur
+    try:
+        ws = ops._ZeroWs.take((64,), like)
+        with torch.cuda.stream(other):
+            with pytest.raises(RuntimeError, match=rf"stream {cur}\b.*stream {other.stream_id}\b"):
+                ops._ZeroWs.give_back_as(ws, like)
+            with pytest.raises(RuntimeError, match=rf"stream {cur}\b.*stream {other.stream_id}\b"):
+                ops._ZeroWs.release(ws)
+        assert ops._ZeroWs.bufs[key][0][1] is True  # (still taken)
+        ws.fill_(3.0)
+        out = ops._ZeroWs.give_back_as(ws, like)
+        assert out.dtype == torch.bfloat16 and bool((out == 3.0).all())
+        assert float(ws.abs().max()) == 0.0 and ops._ZeroWs.bufs[key][0][1] is False
+        again = ops._ZeroWs.take((64,), like)
+        assert again.data_ptr() == ws.data_ptr() and len(ops._ZeroWs.bufs[key]) == 1
+        ops._ZeroWs.release(again)
+    finally:
+        ops._ZeroWs.bufs.pop(key, None)
