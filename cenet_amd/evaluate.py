@@ -291,6 +291,77 @@ def metric_percase(pred: torch.Tensor, gt: torch.Tensor, method: str = "auto") -
     return 0, 0, 0, 0
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# connected-component post-processing (csrc/ccl.hip; not in the reference, off unless asked for)
+# ---------------------------------------------------------------------------------------------------------------------
+POSTPROCESS = (None, "lcc")
+
+
+def _check_postprocess(postprocess):
+    if postprocess not in POSTPROCESS:
+        raise ValueError(f"postprocess: None or 'lcc' (keep the largest connected component of each class) expected, "
+                         f"got {postprocess!r}")
+
+
+def _ccl_volume(label_map: torch.Tensor, classes: int, connectivity: int, per_slice: bool):
+    """the label map as a contiguous fp32 volume [D,H,W] (an image [H,W]: D = 1), refused before anything is allocated"""
+    from . import _lib
+    if label_map.dim() not in (2, 3):
+        raise ValueError(f"a label volume [D,H,W] or image [H,W] expected, got {tuple(label_map.shape)}")
+    if not label_map.is_cuda and not _lib.is_hostsim():
+        raise ValueError("connected components run on the MI355X only: the label map is not on a CUDA/HIP device")
+    shape = (1,) + tuple(label_map.shape) if label_map.dim() == 2 else tuple(label_map.shape)
+    kern._ccl_check(classes, *shape, connectivity, not per_slice)
+    return label_map.reshape(shape).float().contiguous()
+
+
+def _ccl_roots(vol: torch.Tensor, classes: int, connectivity: int, per_slice: bool) -> torch.Tensor:
+    roots = torch.empty(vol.shape, dtype=torch.int32, device=vol.device)
+    kern.ccl_label(vol, roots, classes, *vol.shape, connectivity, not per_slice)
+    return roots
+
+
+def connected_components(label_map: torch.Tensor, classes: int, connectivity: int = 1, per_slice: bool = False) -> torch.Tensor:
+    """Components of every class of a label map [D,H,W] (or [H,W]) at once: int32, same shape, each voxel of class 1..classes-1
+    gets the smallest linear index of its component, background -1.  connectivity 1 / 2 / 3 as
+    scipy.ndimage.generate_binary_structure; per_slice: every slice on its own (connectivity 1 or 2)."""
+    vol = _ccl_volume(label_map, classes, connectivity, per_slice)
+    return _ccl_roots(vol, classes, connectivity, per_slice).reshape(label_map.shape)
+
+
+def component_sizes(roots: torch.Tensor) -> torch.Tensor:
+    """int32, same shape as `roots`: a component's voxel count at its root's position, 0 elsewhere"""
+    roots = roots.contiguous()
+    sizes = torch.empty_like(roots)
+    kern.ccl_sizes(roots, sizes, roots.numel())
+    return sizes
+
+
+def keep_largest_component(label_map: torch.Tensor, classes: int, connectivity: int = 1, per_slice: bool = False,
+                           min_size: int = 0) -> Tuple[torch.Tensor, np.ndarray]:
+    """Keep the largest component of every class (per_slice: of every class in every slice) and set the other voxels to 0; among
+    components of equal size the first in raster order stays.  min_size > 0 also keeps every component of at least that many voxels.
+    -> (filtered fp32 map of the same shape, numpy [classes, 3]: components found, voxels kept, voxels removed per class).
+    One download (the table); a map without foreground comes back as zeros with a zero table."""
+    if min_size < 0:
+        raise ValueError(f"min_size >= 0 expected, got {min_size}")
+    vol = _ccl_volume(label_map, classes, connectivity, per_slice)
+    D, H, W = vol.shape
+    roots = _ccl_roots(vol, classes, connectivity, per_slice)
+    sizes = component_sizes(roots)
+    ws = torch.empty(kern.ccl_ws_ints(classes, D, not per_slice), dtype=torch.int32, device=vol.device)
+    out = torch.empty_like(vol)
+    table = torch.empty((classes, 3), dtype=torch.int32, device=vol.device)
+    kern.ccl_keep(vol, roots, sizes, ws, out, table, classes, D, H, W, not per_slice, min_size)
+    return out.reshape(label_map.shape), _download(table)
+
+
+def _postprocessed(pred_d: torch.Tensor, classes: int, postprocess, connectivity: int, per_slice: bool) -> torch.Tensor:
+    if postprocess is None:
+        return pred_d
+    return keep_largest_component(pred_d, classes, connectivity, per_slice)[0]
+
+
 def _device_case(image, label, device, patch_size):
     """image and label [D, H, W] on the device (one upload each), or None when the device resize does not take the case: a 2-D
     input, or an axis of length 1 that has to be resized (scipy special-cases those; the host path handles them)"""
@@ -381,20 +452,25 @@ def predict_volume(net, volume: torch.Tensor, patch_size: Sequence[int], batch_s
 @torch.no_grad()
 def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int] = (224, 224), batch_slices: int = 32,
                        device=None, resize: str = "host", test_save_path=None, case=None,
-                       z_spacing: float = 1.0) -> List[Tuple[float, float, float, float]]:
+                       z_spacing: float = 1.0, postprocess=None, lcc_connectivity: int = 1,
+                       lcc_per_slice: bool = False) -> List[Tuple[float, float, float, float]]:
     """test_single_volume (metrics_eval.py:37-84) for a 3-D volume: image / label [1,D,H,W] or [D,H,W] (tensor or ndarray).
     Slices are resized to `patch_size` with scipy's cubic zoom and the predictions back with order 0 exactly as the
     reference does (host side), but the network runs on batches of slices and the metrics on the device.
     `resize="device"`: image and label are uploaded once and both resizes run on the device (`predict_volume`); a case the
     device resize does not take (an axis of length 1) goes the host way.  `test_save_path`: see `_save_case`.
+    `postprocess="lcc"`: the prediction goes through `keep_largest_component(pred, classes, lcc_connectivity, lcc_per_slice)` on
+    the device before it is scored and saved (not in the reference; None: no such step).
     Returns [(dice, hd95, jaccard, assd)] for classes 1..classes-1."""
     from scipy.ndimage import zoom
     assert resize in ("host", "device"), resize
+    _check_postprocess(postprocess)
     device = device or next(net.parameters()).device
     net.eval()
     on_dev = _device_case(image, label, device, patch_size) if resize == "device" else None
     if on_dev is not None:
         pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices)
+        pred_d = _postprocessed(pred_d, classes, postprocess, lcc_connectivity, lcc_per_slice)
         if test_save_path is not None:
             _save_case(test_save_path, case, z_spacing, pred_d, on_dev[0], on_dev[1])
         return label_metrics(pred_d, on_dev[1], classes, "acdc")
@@ -417,6 +493,8 @@ def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int
             prediction[s + i] = zoom(out[i], (x / patch_size[0], y / patch_size[1]), order=0) if resize else out[i]
     pred_d = torch.from_numpy(np.ascontiguousarray(prediction)).to(device)
     lab_d = torch.from_numpy(np.ascontiguousarray(label)).to(device)
+    if postprocess is not None:
+        pred_d = prediction = _postprocessed(pred_d, classes, postprocess, lcc_connectivity, lcc_per_slice)
     if test_save_path is not None:
         _save_case(test_save_path, case, z_spacing, prediction, image, label)
     return label_metrics(pred_d, lab_d, classes, "acdc")
@@ -444,21 +522,25 @@ def synapse_metric_percase(pred: torch.Tensor, gt: torch.Tensor, method: str = "
 
 @torch.no_grad()
 def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequence[int] = (256, 256), test_save_path=None,
-                               case=None, z_spacing: float = 1.0, batch_slices: int = 32, device=None, resize: str = "host"):
+                               case=None, z_spacing: float = 1.0, batch_slices: int = 32, device=None, resize: str = "host",
+                               postprocess=None, lcc_connectivity: int = 1, lcc_per_slice: bool = False):
     """test_single_volume of utils_synapse.py:49-97: every slice of the volume [1, D, H, W] is resized to `patch_size` (cubic
     zoom), normalised with Normalize([0.5], [0.5]) (`ToTensor` leaves float arrays unscaled), classified, and the prediction
     resized back with order 0; returns [(dice, hd95)] for classes 1..classes-1.  A 2-D input takes the reference's second branch
     (one forward, no normalisation).  The slices go through the network in batches (with the reference's batch-1 semantics),
     the metrics run on the device.  `test_save_path` (NIfTI files through SimpleITK, which is absent here) writes .npy volumes
     with the spacing (1, 1, z_spacing) in a side-car text file instead.  `resize="device"`: as for `test_single_volume`, with the
-    normalisation inside the resize kernel; the 2-D branch has no resize and is the same in both modes."""
+    normalisation inside the resize kernel; the 2-D branch has no resize and is the same in both modes.  `postprocess`,
+    `lcc_connectivity`, `lcc_per_slice`: as for `test_single_volume`."""
     from scipy.ndimage import zoom
     assert resize in ("host", "device"), resize
+    _check_postprocess(postprocess)
     device = device or next(net.parameters()).device
     net.eval()
     on_dev = _device_case(image, label, device, patch_size) if resize == "device" else None
     if on_dev is not None:
         pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices, normalize=(0.5, 0.5))
+        pred_d = _postprocessed(pred_d, classes, postprocess, lcc_connectivity, lcc_per_slice)
         if test_save_path is not None:
             _save_case(test_save_path, case, z_spacing, pred_d, on_dev[0], on_dev[1])
         return label_metrics(pred_d, on_dev[1], classes, "synapse")
@@ -486,6 +568,8 @@ def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequ
         prediction = pred.squeeze(0).cpu().numpy().astype(label.dtype)
     pred_d = torch.from_numpy(np.ascontiguousarray(prediction)).to(device)
     lab_d = torch.from_numpy(np.ascontiguousarray(label)).to(device)
+    if postprocess is not None:
+        pred_d = prediction = _postprocessed(pred_d, classes, postprocess, lcc_connectivity, lcc_per_slice)
     metric_list = label_metrics(pred_d, lab_d, classes, "synapse")
     if test_save_path is not None:
         _save_case(test_save_path, case, z_spacing, prediction, image, label)
@@ -522,17 +606,23 @@ def val_single_volume(image, label, net, classes: int, patch_size: Sequence[int]
 
 @torch.no_grad()
 def inference(net, volumes, classes: int, patch_size: Sequence[int] = (224, 224), z_spacing: float = 1.0, test_save_path=None,
-              log=print, resize: str = "device", batch_slices: int = 32, device=None) -> Tuple[float, float]:
+              log=print, resize: str = "device", batch_slices: int = 32, device=None, postprocess=None,
+              lcc_connectivity: int = 1, lcc_per_slice: bool = False) -> Tuple[float, float]:
     """inference (utils_acdc.py:7-33): `test_single_volume` for every case of `volumes` (the test loader's dicts: `image`
     [1, D, H, W], `label`, `case_name` — a string or the DataLoader's one-element list), the reference's per-case and per-class
-    log lines through `log`, and (mean dice, mean hd95): the metric table averaged over the cases, then over the classes."""
+    log lines through `log`, and (mean dice, mean hd95): the metric table averaged over the cases, then over the classes.
+    `postprocess`, `lcc_connectivity`, `lcc_per_slice` go to `test_single_volume`."""
+    _check_postprocess(postprocess)
+    post = {} if postprocess is None else dict(postprocess=postprocess, lcc_connectivity=lcc_connectivity,
+                                               lcc_per_slice=lcc_per_slice)
     net.eval()
     total, n = 0.0, 0
     for i, batch in enumerate(volumes):
         case = batch["case_name"]
         case = case[0] if isinstance(case, (list, tuple)) else case
         m = test_single_volume(batch["image"], batch["label"], net, classes, patch_size=patch_size, batch_slices=batch_slices,
-                               device=device, resize=resize, test_save_path=test_save_path, case=case, z_spacing=z_spacing)
+                               device=device, resize=resize, test_save_path=test_save_path, case=case, z_spacing=z_spacing,
+                               **post)
         total = total + np.array(m, dtype=np.float64)
         n += 1
         mm = np.mean(m, axis=0)

@@ -1005,6 +1005,53 @@ def border_gather(bl_u8, match, D, H, W, offs_i32, src_i32, out_i32):
     _call("cenet_border_gather_i32", bl_u8, match, D, H, W, offs_i32, src_i32, out_i32)
 
 
+def ccl_supported(D, H, W) -> bool:
+    return D > 0 and H > 0 and W > 0 and D * H * W < 2 ** 31
+
+
+def _ccl_check(K, D, H, W, connectivity=1, zlinks=True):
+    if not ccl_supported(D, H, W):
+        raise ValueError(f"connected components need positive sides and D*H*W < 2^31, got {(D, H, W)}")
+    if not 2 <= K <= 64:
+        raise ValueError(f"2 <= classes <= 64 expected, got {K}")
+    if connectivity not in (1, 2, 3) or (connectivity == 3 and not zlinks):
+        raise ValueError(f"connectivity 1, 2 or 3 expected (1 or 2 per slice), got {connectivity}")
+
+
+def ccl_label(labels_f32, roots_i32, K, D, H, W, connectivity=1, zlinks=True):
+    """roots [D*H*W] = the smallest linear index of each voxel's component (same class, 6 / 18 / 26 neighbours; zlinks False:
+    in-plane neighbours only), -1 for background (csrc/ccl.hip)"""
+    _ccl_check(K, D, H, W, connectivity, zlinks)
+    _call("cenet_ccl_label_f32", labels_f32, roots_i32, K, D, H, W, connectivity, bool(zlinks))
+
+
+def ccl_sizes(roots_i32, sizes_i32, n):
+    """sizes[r] = voxels of the component with root r, 0 elsewhere (zeroed by the call)"""
+    _call("cenet_ccl_sizes_i32", roots_i32, sizes_i32, n)
+
+
+def ccl_ws_ints(K, D, zlinks=True) -> int:
+    n = _lib.lib().cenet_ccl_ws_ints(K, D, bool(zlinks))
+    if n <= 0:
+        raise ValueError(f"connected components: unsupported K={K} D={D} (2 <= K <= 64)")
+    return n
+
+
+def _overlap(a, b) -> bool:
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def ccl_keep(labels_f32, roots_i32, sizes_i32, ws_i32, out_f32, table_i32, K, D, H, W, zlinks=True, min_size=0):
+    """out = labels where the voxel's component is its class's largest (per slice with zlinks False; ties: the smaller root) or
+    has >= min_size > 0 voxels, else 0; table [K, 3] = components, voxels kept, voxels removed per class.  out may not alias labels."""
+    _ccl_check(K, D, H, W)
+    if _overlap(out_f32, labels_f32):
+        raise ValueError("ccl_keep: out may not alias the label volume")
+    _call("cenet_ccl_keep_f32", labels_f32, roots_i32, sizes_i32, ws_i32, ws_i32.numel(), out_f32, table_i32, K, D, H, W,
+          bool(zlinks), int(min_size))
+
+
 def sgd_step(p, g, buf, hyper5, n, shadow=None):
     """shadow: bf16 copy of the parameters, rewritten by the same kernel (the GEMM operand of the throughput mode)"""
     if shadow is None:

@@ -47,14 +47,15 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
                graph: bool = True, val_batches: Optional[Callable[[], Iterable]] = None, log_every: int = 20,
                log: Callable[[str], None] = print, optimizer: str = "sgd", scheduler: str = "poly",
                test_volumes: Optional[Callable[[], Iterable]] = None, save_dir: Optional[str] = None, img_size: int = 224,
-               test_resize: str = "device", dice_class_weights=None, ce_class_weights=None, ignore_index=None) -> dict:
+               test_resize: str = "device", dice_class_weights=None, ce_class_weights=None, ignore_index=None,
+               test_postprocess=None) -> dict:
     """main_acdc.py:200-290.  tr_loader yields {'image' [B,1,H,W] float, 'label' [B,H,W]} batches (host or device tensors);
     val_batches() yields (image [1,1,H,W], label [1,H,W]) pairs for the per-epoch validation (main_acdc.py:218-231).
     optimizer / scheduler: the reference's --optimizer / --scheduler strings (main_acdc.py:34-35, core.py:12-41); `momentum`
     applies to SGD, Adam / AdamW take betas (0.9, 0.999) and eps 1e-8 as the reference does.
     test_volumes() yields the test loader's dicts (`image` [1,D,H,W], `label`, `case_name`) and needs val_batches: after an
     epoch whose validation Dice is >= the best so far, evaluate.inference runs over them (slices resized to img_size, `test_resize`
-    as evaluate.test_single_volume takes it); only when its Dice is >= the best test Dice do BOTH bests move and `best.pth` is
+    as evaluate.test_single_volume takes it, `test_postprocess` as its `postprocess`: None or "lcc"); only when its Dice is >= the best test Dice do BOTH bests move and `best.pth` is
     written (main_acdc.py:272-278: a validation gain without a test gain moves neither); the last epoch writes
     `epoch=<e>_lr=<lr>_avg_dcs=<last test dice>.pth` (:286-289).  Files go to save_dir (None: none are written).
     -> {'loss': per-iteration losses read back at log points, 'epoch_loss': [...], 'val_dice': [...], 'lr': [...]} and, with
@@ -66,6 +67,7 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
     from . import checkpoint, evaluate
     if test_volumes is not None and val_batches is None:
         raise ValueError("test_volumes: the test inference is gated by the validation Dice, pass val_batches too")
+    evaluate._check_postprocess(test_postprocess)
     if save_dir is not None and test_volumes is None:
         raise ValueError("save_dir: the checkpoints of main_acdc.py:272-289 are written by the test inference, pass test_volumes")
     dev = torch.device(device)
@@ -143,7 +145,8 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
         vl = hist["val_dice"][-1]
         if vl >= best_val:
             te_dice, te_hd = evaluate.inference(net, test_volumes(), num_classes, patch_size=(img_size, img_size), log=log,
-                                                resize=test_resize)
+                                                resize=test_resize,
+                                                **({} if test_postprocess is None else {"postprocess": test_postprocess}))
             net.train()
             if te_dice >= best_test:
                 best_val, best_test = vl, te_dice

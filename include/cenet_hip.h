@@ -595,6 +595,27 @@ int cenet_label_borders_f32(const float* pred, const float* gt, unsigned char* b
 int cenet_border_count_u8(const unsigned char* bl, int match, long n, int* counts, cenet_stream_t stream);
 int cenet_border_gather_i32(const unsigned char* bl, int match, int D, int H, int W, const int* offs, const int* src, int* out,
                             cenet_stream_t stream);
+/* Connected components of a label volume (csrc/ccl.hip; a post-processing step, not in the reference).  labels [D,H,W]: class ids
+ * as float, anything that is not an integer in [1, K) is background.  Two voxels are linked when they are neighbours and carry the
+ * same class; connectivity 1 / 2 / 3 = 6 / 18 / 26 neighbours (scipy.ndimage.generate_binary_structure(3, connectivity)), zlinks
+ * = 0 leaves out every neighbour with a z offset (per-slice 2-D labelling, connectivity 1 or 2 only).  roots [D*H*W] int32: the
+ * smallest linear index z H W + y W + x of the voxel's component, -1 for background — the same bits on every run.
+ * CENET_EINVAL (nothing launched) unless 2 <= K <= 64, D, H, W > 0, D*H*W < 2^31, 1 <= connectivity <= 3 and, with zlinks = 0,
+ * connectivity <= 2. */
+int cenet_ccl_label_f32(const float* labels, int* roots, int K, int D, int H, int W, int connectivity, int zlinks,
+                        cenet_stream_t stream);
+/* sizes [n] int32, zeroed by the call: sizes[r] = voxels of the component with root r (roots as cenet_ccl_label_f32 writes them),
+ * 0 at every voxel that is no root.  CENET_EINVAL unless 0 < n < 2^31. */
+int cenet_ccl_sizes_i32(const int* roots, int* sizes, long n, cenet_stream_t stream);
+/* Keep the largest component of every class — with zlinks = 0 of every (slice, class) — and drop the others: out [D*H*W] = the
+ * voxel's class where its component is the selected one or, when min_size > 0, has at least min_size voxels; 0 elsewhere.  Among
+ * components of equal size the one with the smaller root is selected.  table [K, 3] int32, zeroed by the call: per class the
+ * components found, the voxels kept, the voxels removed.  ws: ws_ints >= cenet_ccl_ws_ints(K, D, zlinks) ints of scratch, filled by
+ * the call.  labels, K, D, H, W, zlinks as given to cenet_ccl_label_f32 for these roots.  CENET_EINVAL (nothing launched) for a
+ * shape that call refuses, a workspace that is too small, min_size < 0, or out == labels. */
+long cenet_ccl_ws_ints(int K, int D, int zlinks);
+int cenet_ccl_keep_f32(const float* labels, const int* roots, const int* sizes, int* ws, long ws_ints, float* out, int* table,
+                       int K, int D, int H, int W, int zlinks, int min_size, cenet_stream_t stream);
 /* torch.optim.SGD(momentum, weight_decay) over a flat arena; hyper5 (device) = [lr, momentum, wd, grad_scale, first_step] */
 int cenet_sgd_step_f32(float* p, const float* g, float* buf, const float* hyper5, long n, cenet_stream_t stream);
 /* torch.optim.Adam / AdamW (amsgrad off) over a flat arena, one pass; exp_avg / exp_avg_sq are the flat fp32 moment buffers.
