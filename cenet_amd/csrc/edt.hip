@@ -10,6 +10,9 @@
 //                          Meijster, Roerdink & Hesselink (2000), one thread per line, consecutive lanes = consecutive x
 //   border_count / border_gather   order-preserving compaction of a border: coordinates (for the all-pairs kernel) or the
 //                          transform's values in C order of the border voxels
+//   dm_labels / dm_logits / dm_merge   boundary-distance maps of a stack of 2-D class planes for the distance-map losses
+//                          (dist_loss.hip): the planes' masks and their complements as one stack of features, the x and y passes
+//                          above over that stack, and the sum of the two halves
 #include "common.h"
 #include "../../include/cenet_hip.h"
 
@@ -261,20 +264,142 @@ extern "C" int cenet_label_borders_f32(const float* pred, const float* gt, unsig
   return CENET_OK;
 }
 
+// The in-plane transform of `planes` planes of H x W: the x pass over planes * H rows into xd, then the line pass along y with
+// blockIdx.y = plane into out.  A volume is this plus the z pass; a stack of unrelated planes is this alone.  planes <= 65535.
+static int edt_planes_launch(const unsigned char* feat, int match, int* xd, int* out, int planes, int H, int W, hipStream_t stream) {
+  const long rows = (long)planes * H, plane = (long)H * W;
+  CENET_LAUNCH(edt_x_kernel, dim3(edt_cdiv(rows, EX_ROWS)), dim3(256), stream, feat, match, xd, rows, W);
+  CENET_CHECK_LAUNCH();
+  CENET_LAUNCH(edt_line_kernel, dim3(edt_cdiv(W, 64), (unsigned)planes), dim3(64), stream, (const int*)xd, out, (long)W, plane, H,
+               (long)W);
+  CENET_CHECK_LAUNCH();
+  return CENET_OK;
+}
+
 extern "C" int cenet_edt_sq_u8(const unsigned char* feat, int match, int* tmp, int* d2, int D, int H, int W, hipStream_t stream) {
   if (D <= 0 || H <= 0 || W <= 0 || match > 255) return CENET_EINVAL;
   if ((long)D * D + (long)H * H + (long)W * W >= (1L << 31)) return CENET_EINVAL;  // (so every side is < 65536 as well)
   const long rows = (long)D * H, plane = (long)H * W;
   if (plane * D >= (1L << 40) || edt_cdiv(rows, EX_ROWS) == 0) return CENET_EINVAL;
-  CENET_LAUNCH(edt_x_kernel, dim3(edt_cdiv(rows, EX_ROWS)), dim3(256), stream, feat, match, d2, rows, W);
-  CENET_CHECK_LAUNCH();
-  CENET_LAUNCH(edt_line_kernel, dim3(edt_cdiv(W, 64), (unsigned)D), dim3(64), stream, (const int*)d2, tmp, (long)W, plane, H,
-               (long)W);
-  CENET_CHECK_LAUNCH();
+  const int rc = edt_planes_launch(feat, match, d2, tmp, D, H, W, stream);
+  if (rc != CENET_OK) return rc;
   CENET_LAUNCH(edt_line_kernel, dim3(edt_cdiv(plane, 64), 1u), dim3(64), stream, (const int*)tmp, d2, plane, 0L, D, plane);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
 }
+
+// ---- boundary-distance maps --------------------------------------------------------------------------------------------------
+// Plane (b, c), c = 1 .. K-1, has the mask M = {label == c} or {softmax_c > 1/2}.  The map is the squared distance to the nearest
+// pixel of the other kind: the transform with M as features (non-zero outside M) plus the one with the complement as features
+// (non-zero inside M).  Both run as ONE stack of 2 P planes, P = B (K-1): planes [0, P) hold M, planes [P, 2P) its complement.
+// A plane whose M is empty or full has one half without a feature, INT_MAX everywhere, and the other half 0 everywhere:
+// INT_MAX counts as 0 in the sum, so such a plane comes out 0 — decided per pixel on the device, nothing is read back.
+// ws (ints): xd [2 P H W], yd [2 P H W], then the feature bytes [2 P H W].
+#define DM_MAXK 16
+static inline bool dm_shape_ok(int B, int K, int H, int W) {
+  return B > 0 && K >= 2 && K <= DM_MAXK && H >= 1 && W >= 1 && 2L * B * (K - 1) <= 65535 &&
+         (long)H * H + (long)W * W < (1L << 31);
+}
+extern "C" long cenet_dist_maps_ws_ints(int B, int K, int H, int W) {
+  if (!dm_shape_ok(B, K, H, W)) return 0;
+  const long n2 = 2L * B * (K - 1) * H * W;
+  return 2 * n2 + (n2 + 3) / 4;
+}
+
+// one thread per pixel of an image: its K - 1 bytes of M and of the complement, consecutive lanes on consecutive pixels
+__global__ __launch_bounds__(256) void dm_labels_kernel(const float* __restrict__ labels, unsigned char* __restrict__ feat, int K,
+                                                        long HW, long half) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= HW) return;
+  const long b = blockIdx.y;
+  const float t = labels[b * HW + p];
+  unsigned char* f = feat + b * (K - 1) * HW + p;
+  for (int c = 1; c < K; ++c) {
+    const unsigned char m = t == (float)c;
+    f[(c - 1) * HW] = m;
+    f[half + (c - 1) * HW] = m ^ 1;
+  }
+}
+// softmax_c > 1/2  <=>  exp(v_c - max) > sum / 2, in fp32 from the logits; no probability is stored
+template <typename T, int KM>
+__global__ __launch_bounds__(256) void dm_logits_kernel(const T* __restrict__ logits, unsigned char* __restrict__ feat, int K,
+                                                        long HW, long half) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= HW) return;
+  const long b = blockIdx.y;
+  const T* lg = logits + b * K * HW + p;
+  float v[KM];
+  float mx = -3.4e38f;
+#pragma unroll
+  for (int c = 0; c < KM; ++c)
+    if (c < K) {
+      v[c] = ldf(lg + c * HW);
+      mx = fmaxf(mx, v[c]);
+    }
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < KM; ++c)
+    if (c < K) {
+      v[c] = expf(v[c] - mx);
+      s += v[c];
+    }
+  unsigned char* f = feat + b * (K - 1) * HW + p;
+#pragma unroll
+  for (int c = 1; c < KM; ++c)
+    if (c < K) {
+      const unsigned char m = v[c] > 0.5f * s;
+      f[(c - 1) * HW] = m;
+      f[half + (c - 1) * HW] = m ^ 1;
+    }
+}
+__global__ __launch_bounds__(256) void dm_merge_kernel(const int* __restrict__ yd, int* __restrict__ d2, long n) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const int a = yd[i], b = yd[n + i];
+    d2[i] = (a == EDT_INF ? 0 : a) + (b == EDT_INF ? 0 : b);
+  }
+}
+
+// the stack's transform and the sum of its halves, after one of the two kernels above has filled the feature bytes
+static int dm_finish(int* ws, int* d2, int B, int K, int H, int W, hipStream_t stream) {
+  const int P = B * (K - 1);
+  const long n = (long)P * H * W;
+  const int rc = edt_planes_launch((const unsigned char*)(ws + 4 * n), 1, ws, ws + 2 * n, 2 * P, H, W, stream);
+  if (rc != CENET_OK) return rc;
+  long blocks = (n + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  CENET_LAUNCH(dm_merge_kernel, dim3((unsigned)blocks), dim3(256), stream, (const int*)(ws + 2 * n), d2, n);
+  CENET_CHECK_LAUNCH();
+  return CENET_OK;
+}
+static inline bool dm_args_ok(const void* src, int* ws, long ws_ints, int* d2, int B, int K, int H, int W) {
+  return dm_shape_ok(B, K, H, W) && src && ws && d2 && ws_ints >= cenet_dist_maps_ws_ints(B, K, H, W) &&
+         ((long)H * W + 255) / 256 <= 0x7fffffffL;
+}
+
+extern "C" int cenet_dist_maps_labels_f32(const float* labels, int* ws, long ws_ints, int* d2, int B, int K, int H, int W,
+                                          hipStream_t stream) {
+  if (!dm_args_ok(labels, ws, ws_ints, d2, B, K, H, W)) return CENET_EINVAL;
+  const long HW = (long)H * W, n = (long)B * (K - 1) * HW;
+  CENET_LAUNCH(dm_labels_kernel, dim3(edt_cdiv(HW, 256), (unsigned)B), dim3(256), stream, labels, (unsigned char*)(ws + 4 * n), K,
+               HW, n);
+  CENET_CHECK_LAUNCH();
+  return dm_finish(ws, d2, B, K, H, W, stream);
+}
+
+template <typename T>
+static int dist_maps_logits_impl(const T* logits, int* ws, long ws_ints, int* d2, int B, int K, int H, int W, hipStream_t stream) {
+  if (!dm_args_ok(logits, ws, ws_ints, d2, B, K, H, W)) return CENET_EINVAL;
+  const long HW = (long)H * W, n = (long)B * (K - 1) * HW;
+  const dim3 grid(edt_cdiv(HW, 256), (unsigned)B);
+  unsigned char* feat = (unsigned char*)(ws + 4 * n);
+  if (K <= 4) CENET_LAUNCH((dm_logits_kernel<T, 4>), grid, dim3(256), stream, logits, feat, K, HW, n);
+  else if (K <= 9) CENET_LAUNCH((dm_logits_kernel<T, 9>), grid, dim3(256), stream, logits, feat, K, HW, n);
+  else CENET_LAUNCH((dm_logits_kernel<T, DM_MAXK>), grid, dim3(256), stream, logits, feat, K, HW, n);
+  CENET_CHECK_LAUNCH();
+  return dm_finish(ws, d2, B, K, H, W, stream);
+}
+CENET_TWIN(dist_maps_logits, (const T* logits, int* ws, long ws_ints, int* d2, int B, int K, int H, int W, hipStream_t stream),
+           (logits, ws, ws_ints, d2, B, K, H, W, stream))
 
 extern "C" int cenet_border_count_u8(const unsigned char* bl, int match, long n, int* counts, hipStream_t stream) {
   if (n <= 0 || match < 0 || match > 255) return CENET_EINVAL;

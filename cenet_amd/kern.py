@@ -1052,6 +1052,81 @@ def ccl_keep(labels_f32, roots_i32, sizes_i32, ws_i32, out_f32, table_i32, K, D,
           bool(zlinks), int(min_size))
 
 
+def dist_maps_supported(B, K, H, W) -> bool:
+    """what cenet_dist_maps_* takes: 2 B (K-1) planes (every mask and its complement) in one launch grid, int32 distances"""
+    return B >= 1 and 2 <= K <= 16 and H >= 1 and W >= 1 and 2 * B * (K - 1) <= 65535 and H * H + W * W < 2 ** 31
+
+
+def _dist_check(what, B, K, H, W):
+    if not 2 <= K <= 16:
+        raise ValueError(f"{what}: 2 <= classes <= 16 expected, got {K}")
+    if not dist_maps_supported(B, K, H, W):
+        raise ValueError(f"{what}: positive sides, 2 B (K-1) <= 65535 planes and H^2 + W^2 < 2^31 expected, got {(B, K, H, W)}")
+
+
+def dist_maps_ws_ints(B, K, H, W) -> int:
+    """ints of scratch cenet_dist_maps_* needs: two int32 planes and one byte per pixel of the 2 B (K-1) planes"""
+    _dist_check("dist_maps", B, K, H, W)
+    return _lib.lib().cenet_dist_maps_ws_ints(B, K, H, W)
+
+
+def _dist_maps(name, src, n_src, ws_i32, d2_i32, B, K, H, W):
+    _dist_check("dist_maps", B, K, H, W)
+    if src.numel() != n_src or d2_i32.numel() != B * (K - 1) * H * W:
+        raise ValueError(f"dist_maps: {n_src} input and {B * (K - 1) * H * W} output elements expected for {(B, K, H, W)}, got "
+                         f"{src.numel()} and {d2_i32.numel()}")
+    if _overlap(d2_i32, ws_i32) or _overlap(d2_i32, src) or _overlap(ws_i32, src):
+        raise ValueError("dist_maps: input, workspace and output may not alias")
+    _call(name, src, ws_i32, ws_i32.numel(), d2_i32, B, K, H, W)
+
+
+def dist_maps_labels(labels_f32, ws_i32, d2_i32, B, K, H, W):
+    """d2 [B,K-1,H,W] int32 = squared distance of every pixel to the nearest pixel of the other kind, for the masks
+    {label == c}, c = 1 .. K-1; 0 on a plane whose mask is empty or full (csrc/edt.hip).  No sync, same bits on every run."""
+    _dist_maps("cenet_dist_maps_labels_f32", labels_f32, B * H * W, ws_i32, d2_i32, B, K, H, W)
+
+
+def dist_maps_logits(logits, ws_i32, d2_i32, B, K, H, W):
+    """the same for the masks {softmax_c > 1/2} of fp32 or bf16 logits [B,K,H,W]"""
+    _dist_maps("cenet_dist_maps_logits_f32", logits, B * K * H * W, ws_i32, d2_i32, B, K, H, W)
+
+
+def dist_loss_ws_floats(B, K, H, W) -> int:
+    """floats of workspace cenet_dist_loss_fwd needs: one row of two partial sums per forward workgroup"""
+    n = _lib.lib().cenet_dist_loss_ws_floats(B, K, H, W)
+    if n <= 0:
+        raise ValueError(f"dist_loss: unsupported shape B={B} K={K} H={H} W={W} (2 <= K <= 16)")
+    return n
+
+
+def _dist_loss_check(logits, labels, d2g, d2p, w, B, K, H, W, surface, hausdorff):
+    if not (surface or hausdorff):
+        raise ValueError("dist_loss: neither the surface nor the Hausdorff term is present")
+    if not 2 <= K <= 16 or B < 1 or H < 1 or W < 1:
+        raise ValueError(f"dist_loss: unsupported shape B={B} K={K} H={H} W={W} (2 <= K <= 16)")
+    n = B * (K - 1) * H * W
+    if logits.numel() != B * K * H * W or labels.numel() != B * H * W or d2g.numel() != n or w.numel() != 2:
+        raise ValueError(f"dist_loss: tensor sizes do not match {(B, K, H, W)}")
+    if hausdorff and (d2p is None or d2p.numel() != n):
+        raise ValueError("dist_loss: the Hausdorff term needs the prediction's distance maps [B,K-1,H,W]")
+
+
+def dist_loss_fwd(logits, labels, d2g, d2p, w, ws, loss, B, K, H, W, surface, hausdorff):
+    """loss[0] = w[0] L_surf + w[1] L_hd (include/cenet_hip.h spells them out); w: fp32 [2] on the device, read by the kernels;
+    d2p is passed on only with the Hausdorff term"""
+    _dist_loss_check(logits, labels, d2g, d2p, w, B, K, H, W, surface, hausdorff)
+    _call("cenet_dist_loss_fwd_f32", logits, labels, d2g, d2p if hausdorff else None, w, ws, ws.numel(), loss, B, K, H, W,
+          int(bool(surface)), int(bool(hausdorff)))
+
+
+def dist_loss_bwd(logits, labels, d2g, d2p, w, gout, dlogits, B, K, H, W, surface, hausdorff):
+    _dist_loss_check(logits, labels, d2g, d2p, w, B, K, H, W, surface, hausdorff)
+    if dlogits.numel() != logits.numel() or _overlap(dlogits, logits):
+        raise ValueError("dist_loss: dlogits has the logits' size and may not alias them")
+    _call("cenet_dist_loss_bwd_f32", logits, labels, d2g, d2p if hausdorff else None, w, gout, dlogits, B, K, H, W,
+          int(bool(surface)), int(bool(hausdorff)))
+
+
 def sgd_step(p, g, buf, hyper5, n, shadow=None):
     """shadow: bf16 copy of the parameters, rewritten by the same kernel (the GEMM operand of the throughput mode)"""
     if shadow is None:

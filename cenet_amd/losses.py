@@ -7,6 +7,11 @@ BoundaryDoULoss come from the same pass over the labels, and the backward is a s
 Class weights (DiceLoss.forward's `weight`, CrossEntropyLoss's `weight`), `ignore_index`, JaccardLoss (core.py:134-158) and
 DiceLoss(softmax=False) go through cenet_amd.ops.seg_loss (csrc/seg_loss_ex.hip): the same one pass, partial sums stored per
 workgroup and added in a fixed order instead of float atomics.  A call that uses none of them keeps the first path.
+
+The distance-map losses `surface` (Kervadec et al. 2019) and `hausdorff` (Karimi & Salcudean 2019, alpha = 2) go through
+cenet_amd.ops.dist_loss: the exact distance maps of every label map (and, for `hausdorff`, of the thresholded prediction) are
+built on the device inside the step (csrc/edt.hip) and one fused kernel each way reads them (csrc/dist_loss.hip).  They are
+not in the reference; a Criterion that names neither launches nothing of this.
 """
 from __future__ import annotations
 
@@ -54,6 +59,31 @@ class JaccardLoss(nn.Module):
         return ops.seg_loss(input, target, w_jaccard=1.0, ignore_index=self.ignore_index, jaccard_smooth=self.smooth)
 
 
+class SurfaceLoss(nn.Module):
+    """The surface (boundary) loss of Kervadec et al. 2019 over the foreground classes: the mean of softmax probability times
+    the signed distance to the ground-truth contour (+ distance outside the class, -(distance - 1) inside).  inputs [B,K,H,W]
+    logits, target [B,H,W] class ids as floats."""
+
+    def __init__(self, n_classes):
+        super().__init__()
+        self.n_classes = n_classes
+
+    def forward(self, inputs, target):
+        return ops.dist_loss(inputs, target, (1.0, 0.0), surface=True, hausdorff=False)
+
+
+class HausdorffDTLoss(nn.Module):
+    """The distance-transform Hausdorff loss of Karimi & Salcudean 2019 with alpha = 2 over the foreground classes: the mean of
+    (p - g)^2 times the sum of the squared distance maps of the ground truth and of the prediction thresholded at 1/2."""
+
+    def __init__(self, n_classes):
+        super().__init__()
+        self.n_classes = n_classes
+
+    def forward(self, inputs, target):
+        return ops.dist_loss(inputs, target, (0.0, 1.0), surface=False, hausdorff=True)
+
+
 def _class_weights(value, K, name):
     """None, a comma string or a sequence of K floats -> None or a list of K floats"""
     if value is None:
@@ -70,7 +100,11 @@ class Criterion(nn.Module):
     jaccard_smooth (default 1.0).  Without any of them and without `jaccard` the call is ops.dice_ce_loss as before.
     The class weights are uploaded at construction into the buffer `class_weights` ([2K]: Dice, then CE), which follows
     .to(); writing new values into it takes effect at the next call, inside a captured graph too.
-    CE over a batch whose every pixel is ignored is NaN (as torch.nn.CrossEntropyLoss); boundary + ignore_index is refused."""
+    CE over a batch whose every pixel is ignored is NaN (as torch.nn.CrossEntropyLoss); boundary + ignore_index is refused.
+    `surface` and `hausdorff` (SurfaceLoss, HausdorffDTLoss) are two more loss names: their term is added to the total of the
+    other names (which is not computed when none of them is named).  Their weights live in the buffer `dist_weights` ([2]:
+    surface, hausdorff), read on the device by every call; set_dist_weights() writes into it without a sync, so a weight
+    schedule costs a captured step no recapture.  Either name with ignore_index is refused, as boundary is."""
 
     def __init__(self, num_classes, args):
         super().__init__()
@@ -79,7 +113,15 @@ class Criterion(nn.Module):
         weights = [float(w) for w in args.loss_weights.split(',')]
         self.w_dice = self.w_ce = self.w_bd = self.w_jac = 0.0
         has_jaccard = False
+        self.has_base = self.has_surface = self.has_hausdorff = False
+        w_dist = [0.0, 0.0]
         for n, w in zip(names, weights):
+            if n in ("surface", "hausdorff"):
+                w_dist[1 if n == "hausdorff" else 0] += w
+                self.has_surface = self.has_surface or n == "surface"
+                self.has_hausdorff = self.has_hausdorff or n == "hausdorff"
+                continue
+            self.has_base = True
             if n == "dice":
                 self.w_dice += w
             elif n == "ce":
@@ -101,13 +143,38 @@ class Criterion(nn.Module):
         if self.ignore_index is not None and self.w_bd != 0.0:
             raise NotImplementedError("Loss boundary with ignore_index not implemented: the reference defines no boundary count "
                                       "over a label mask with holes")
+        if self.ignore_index is not None and (self.has_surface or self.has_hausdorff):
+            raise NotImplementedError("Loss surface / hausdorff with ignore_index not implemented: a distance map over a label "
+                                      "mask with holes is not defined")
+        if self.has_surface or self.has_hausdorff:
+            self.register_buffer("dist_weights", torch.tensor(w_dist, dtype=torch.float32))
+        else:
+            self.dist_weights = None
         if wd is not None or wc is not None:
             ones = [1.0] * num_classes
             self.register_buffer("class_weights", torch.tensor((wd or ones) + (wc or ones), dtype=torch.float32))
         else:
             self.class_weights = None
 
+    def set_dist_weights(self, surface=None, hausdorff=None):
+        """new weights of the `surface` / `hausdorff` terms (None: unchanged), written into `dist_weights` on its device by a fill
+        launch each: no sync, and the next call — a graph replay included — reads them"""
+        if self.dist_weights is None:
+            raise ValueError("set_dist_weights: loss_type names neither surface nor hausdorff")
+        with torch.no_grad():
+            for i, v in enumerate((surface, hausdorff)):
+                if isinstance(v, torch.Tensor):
+                    self.dist_weights[i].copy_(v.reshape(()), non_blocking=True)
+                elif v is not None:
+                    self.dist_weights[i].fill_(float(v))
+
     def forward(self, outputs, labels):
+        if self.dist_weights is None:
+            return self._base(outputs, labels)
+        dist = ops.dist_loss(outputs, labels, self.dist_weights, surface=self.has_surface, hausdorff=self.has_hausdorff)
+        return self._base(outputs, labels) + dist if self.has_base else dist
+
+    def _base(self, outputs, labels):
         if not self.extended:
             return ops.dice_ce_loss(outputs, labels, self.w_dice, self.w_ce, self.w_bd)
         K, cw = self.num_classes, self.class_weights

@@ -177,4 +177,101 @@ def seg_loss(logits, labels, *, w_dice=0., w_ce=0., w_boundary=0., w_jaccard=0.,
     return SegLossExFn.apply(logits, labels, cw, cfg)
 
 
-__all__ = ["DsebCombineFn", "dseb_combine", "DiceCELossFn", "dice_ce_loss", "SegLossExFn", "class_weight_buffer", "seg_loss"]
+# =====================================================================================================
+# distance-map losses (csrc/edt.hip cenet_dist_maps_*, csrc/dist_loss.hip; not in the reference)
+# =====================================================================================================
+def _dist_shapes(logits, labels, what):
+    if logits is not None and logits.dim() != 4:
+        raise ValueError(f"{what}: logits [B,K,H,W] expected, got {tuple(logits.shape)}")
+    if labels is not None and labels.dim() != 3:
+        raise ValueError(f"{what}: labels [B,H,W] expected, got {tuple(labels.shape)}")
+    if logits is not None and labels is not None and labels.shape != (logits.shape[0],) + tuple(logits.shape[2:]):
+        raise ValueError(f"{what}: logits [B,K,H,W] and labels [B,H,W], got {tuple(logits.shape)} and {tuple(labels.shape)}")
+    for t in (logits, labels):
+        if t is not None and not t.is_cuda and not kern._lib.is_hostsim():
+            raise ValueError(f"{what}: the distance-map losses run on the MI355X only: tensor is not on a CUDA/HIP device")
+
+
+def distance_maps(labels: Tensor, K: int) -> Tensor:
+    """labels [B,H,W] (class ids as floats) -> int32 [B,K-1,H,W]: for every foreground class c the exact squared Euclidean
+    distance of each pixel to the nearest pixel of the other kind of the mask {label == c} (inside: to the nearest pixel
+    outside, outside: to the nearest pixel of the class); 0 on a plane whose class is absent or fills it.  A handful of launches,
+    no sync, the same bits on every run."""
+    _dist_shapes(None, labels, "distance_maps")
+    B, H, W = labels.shape
+    labels = _c(labels.float())
+    ws = _empty((kern.dist_maps_ws_ints(B, K, H, W),), labels, torch.int32)
+    d2 = _empty((B, K - 1, H, W), labels, torch.int32)
+    kern.dist_maps_labels(labels, ws, d2, B, K, H, W)
+    return d2
+
+
+def pred_distance_maps(logits: Tensor) -> Tensor:
+    """logits [B,K,H,W] (fp32 or bf16) -> the same maps for the thresholded prediction {softmax_c > 1/2}, c = 1 .. K-1"""
+    _dist_shapes(logits, None, "pred_distance_maps")
+    B, K, H, W = logits.shape
+    logits = _c(logits.detach())
+    ws = _empty((kern.dist_maps_ws_ints(B, K, H, W),), logits, torch.int32)
+    d2 = _empty((B, K - 1, H, W), logits, torch.int32)
+    kern.dist_maps_logits(logits, ws, d2, B, K, H, W)
+    return d2
+
+
+class DistLossFn(Function):
+    """w[0] * surface loss + w[1] * Hausdorff-DT loss (csrc/dist_loss.hip; include/cenet_hip.h spells the terms out).  The maps
+    are built inside the forward (the prediction's only with the Hausdorff term) and kept for the backward as constants.
+    w: fp32 [2] on the device, read by the kernels; the gradient goes to `logits` only."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, w, surface, hausdorff):
+        logits, labels = _c(logits), _c(labels)
+        B, K, H, W = logits.shape
+        d2g = distance_maps(labels, K)
+        d2p = pred_distance_maps(logits) if hausdorff else None
+        ws = _empty((kern.dist_loss_ws_floats(B, K, H, W),), logits)
+        loss = _empty((1,), logits)
+        kern.dist_loss_fwd(logits, labels, d2g, d2p, w, ws, loss, B, K, H, W, surface, hausdorff)
+        ctx.save_for_backward(logits, labels, d2g, w, *(() if d2p is None else (d2p,)))
+        ctx.cfg = (surface, hausdorff)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, d2g, w, *rest = ctx.saved_tensors
+        surface, hausdorff = ctx.cfg
+        B, K, H, W = logits.shape
+        d = torch.empty_like(logits)
+        kern.dist_loss_bwd(logits, labels, d2g, rest[0] if rest else None, w, _c(g).reshape(1).float(), d, B, K, H, W, surface,
+                           hausdorff)
+        return d, None, None, None, None
+
+
+_DIST_WEIGHTS: dict = {}  # (device, w_surface, w_hausdorff) -> the [2] device buffer uploaded for them
+
+
+def dist_loss(logits, labels, weights, *, surface=True, hausdorff=True):
+    """loss = weights[0] * surface loss + weights[1] * Hausdorff-DT loss (alpha = 2) on logits [B,K,H,W] (fp32 or bf16) and labels
+    [B,H,W] (class ids as floats in [0,K)), both over the foreground classes 1 .. K-1.  weights: a pair of floats, uploaded once
+    per pair of values and cached, or an fp32 [2] tensor on the logits' device, used as it is (a later write into it is seen by
+    the next call, a graph replay included).  surface / hausdorff: which terms are present; an absent term costs nothing — without
+    the Hausdorff term the prediction's distance maps are not built."""
+    if not (surface or hausdorff):
+        raise ValueError("dist_loss: neither the surface nor the Hausdorff term is present")
+    _dist_shapes(logits, labels, "dist_loss")
+    if isinstance(weights, Tensor):
+        if weights.dtype != torch.float32 or weights.device != logits.device or weights.numel() != 2 or not weights.is_contiguous():
+            raise ValueError(f"dist_loss: weights: a contiguous fp32 [2] tensor on {logits.device} expected, got "
+                             f"{weights.dtype} {tuple(weights.shape)} on {weights.device}")
+        w = weights.detach().reshape(2)
+    else:
+        if len(weights) != 2:
+            raise ValueError(f"dist_loss: weights: (surface, hausdorff) expected, got {len(weights)} values")
+        key = (str(logits.device), float(weights[0]), float(weights[1]))
+        w = _DIST_WEIGHTS.get(key)
+        if w is None:
+            w = _DIST_WEIGHTS[key] = torch.tensor(key[1:], dtype=torch.float32).to(logits.device)
+    return DistLossFn.apply(logits, labels.float(), w, bool(surface), bool(hausdorff))
+
+
+__all__ = ["DsebCombineFn", "dseb_combine", "DiceCELossFn", "dice_ce_loss", "SegLossExFn", "class_weight_buffer", "seg_loss",
+           "distance_maps", "pred_distance_maps", "DistLossFn", "dist_loss"]

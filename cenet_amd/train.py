@@ -48,7 +48,7 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
                log: Callable[[str], None] = print, optimizer: str = "sgd", scheduler: str = "poly",
                test_volumes: Optional[Callable[[], Iterable]] = None, save_dir: Optional[str] = None, img_size: int = 224,
                test_resize: str = "device", dice_class_weights=None, ce_class_weights=None, ignore_index=None,
-               test_postprocess=None) -> dict:
+               test_postprocess=None, dist_weight_schedule: Optional[Callable[[int], tuple]] = None) -> dict:
     """main_acdc.py:200-290.  tr_loader yields {'image' [B,1,H,W] float, 'label' [B,H,W]} batches (host or device tensors);
     val_batches() yields (image [1,1,H,W], label [1,H,W]) pairs for the per-epoch validation (main_acdc.py:218-231).
     optimizer / scheduler: the reference's --optimizer / --scheduler strings (main_acdc.py:34-35, core.py:12-41); `momentum`
@@ -61,7 +61,11 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
     -> {'loss': per-iteration losses read back at log points, 'epoch_loss': [...], 'val_dice': [...], 'lr': [...]} and, with
     test_volumes, 'test_dice' / 'test_hd95' (one entry per inference run) and 'best_epochs' (epochs that wrote best.pth)
     loss_type may name `jaccard`; dice_class_weights / ce_class_weights (comma string or num_classes floats) and ignore_index
-    are losses.Criterion's optional attributes of the same names (None: the loss path without them)"""
+    are losses.Criterion's optional attributes of the same names (None: the loss path without them).
+    loss_type may also name `surface` and `hausdorff` (the distance-map losses, their weights in loss_weights);
+    dist_weight_schedule: epoch -> (w_surface, w_hausdorff), called at the start of every epoch and handed to
+    Criterion.set_dist_weights — the weights are read on the device, so the captured step is replayed, not recaptured
+    (Kervadec's rebalancing moves the surface weight every epoch)"""
     import os
 
     from . import checkpoint, evaluate
@@ -74,6 +78,8 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
     net = net.to(dev).train()
     crit = losses.Criterion(num_classes, criterion_args(loss_type, loss_weights, dice_class_weights, ce_class_weights,
                                                         ignore_index)).to(dev)
+    if dist_weight_schedule is not None and crit.dist_weights is None:
+        raise ValueError("dist_weight_schedule: loss_type names neither surface nor hausdorff")
     arena = optim.ParamArena(net, optim.cenet_segments())
     if optimizer.lower() == "sgd":
         opt = optim.FusedSGD(arena, lr=base_lr, momentum=momentum, weight_decay=weight_decay)
@@ -120,6 +126,8 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
     it = 0
     for epoch in range(max_epochs):
         net.train()
+        if dist_weight_schedule is not None:
+            crit.set_dist_weights(*dist_weight_schedule(epoch))
         run = torch.zeros((), device=dev)
         n_img = 0
         for batch in DevicePrefetcher(_as_batches(tr_loader), dev):

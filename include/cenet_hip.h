@@ -616,6 +616,39 @@ int cenet_ccl_sizes_i32(const int* roots, int* sizes, long n, cenet_stream_t str
 long cenet_ccl_ws_ints(int K, int D, int zlinks);
 int cenet_ccl_keep_f32(const float* labels, const int* roots, const int* sizes, int* ws, long ws_ints, float* out, int* table,
                        int K, int D, int H, int W, int zlinks, int min_size, cenet_stream_t stream);
+/* Boundary-distance maps for the distance-map losses (csrc/edt.hip; not in the reference).  For every image b and foreground class
+ * c = 1 .. K-1 the plane (b, c) has a mask M: {label == c} for the labels [B,H,W] (class ids as floats), {softmax_c > 1/2} for the
+ * logits [B,K,H,W] (the threshold is taken in fp32 from the logits, no probability is stored).  d2 [B, K-1, H, W] int32:
+ * the squared Euclidean distance, unit spacing, exact, from the pixel to the nearest pixel of the OTHER kind — the nearest pixel
+ * outside M for a pixel of M, the nearest pixel of M otherwise (scipy: distance_transform_edt(M)^2 + distance_transform_edt(~M)^2).
+ * A plane whose M is empty or the whole plane is 0 everywhere.  Integer arithmetic only, no atomics: the same bits on every run;
+ * nothing is read back.  ws: ws_ints >= cenet_dist_maps_ws_ints(B, K, H, W) ints of scratch.  CENET_EINVAL (nothing launched)
+ * unless 2 <= K <= 16, B, H, W >= 1, 2 B (K-1) <= 65535, H^2 + W^2 < 2^31 and the workspace is large enough. */
+long cenet_dist_maps_ws_ints(int B, int K, int H, int W);
+int cenet_dist_maps_labels_f32(const float* labels, int* ws, long ws_ints, int* d2, int B, int K, int H, int W,
+                               cenet_stream_t stream);
+int cenet_dist_maps_logits_f32(const float* logits, int* ws, long ws_ints, int* d2, int B, int K, int H, int W,
+                               cenet_stream_t stream);
+/* The distance-map losses on those maps (csrc/dist_loss.hip): the surface (boundary) loss of Kervadec et al. 2019 and the
+ * Hausdorff-DT loss of Karimi & Salcudean 2019 with alpha = 2.  With N = B (K-1) H W, p = softmax(logits) over the K planes,
+ * g_c = [label == c], d2g / d2p the maps of the labels / of the logits, and sums over b, c = 1 .. K-1 and the pixels:
+ *   phi_c  = +sqrt(d2g_c) outside class c, -(sqrt(d2g_c) - 1) inside      (the signed distance of Kervadec's one_hot2dist)
+ *   L_surf = 1/N sum p_c phi_c
+ *   L_hd   = 1/N sum (p_c - g_c)^2 (d2g_c + d2p_c)                        (d2p is a constant: no gradient through the threshold)
+ *   loss   = w[0] L_surf + w[1] L_hd
+ * w: two floats in device memory, read by the kernels of every launch.  surface / hausdorff: which terms are present (one at
+ * least); a term that is absent is left out, and without the Hausdorff term d2p is not read (may be NULL).  Forward: one pass that
+ * stores a row of two partial sums per workgroup in ws (ws_floats >= cenet_dist_loss_ws_floats(B, K, H, W)) and a one-workgroup
+ * launch that adds the rows in a fixed order — no float atomics, bitwise reproducible.  Backward: with a_0 = 0 and
+ * a_j = w[0] phi_j + 2 w[1] (p_j - g_j)(d2g_j + d2p_j),  dlogits_j = gout[0] p_j (a_j - sum_c p_c a_c) / N.
+ * CENET_EINVAL unless 2 <= K <= 16, 1 <= B <= 65535, H, W >= 1. */
+long cenet_dist_loss_ws_floats(int B, int K, int H, int W);
+int cenet_dist_loss_fwd_f32(const float* logits, const float* labels, const int* d2g, const int* d2p, const float* w, float* ws,
+                            long ws_floats, float* loss, int B, int K, int H, int W, int surface, int hausdorff,
+                            cenet_stream_t stream);
+int cenet_dist_loss_bwd_f32(const float* logits, const float* labels, const int* d2g, const int* d2p, const float* w,
+                            const float* gout, float* dlogits, int B, int K, int H, int W, int surface, int hausdorff,
+                            cenet_stream_t stream);
 /* torch.optim.SGD(momentum, weight_decay) over a flat arena; hyper5 (device) = [lr, momentum, wd, grad_scale, first_step] */
 int cenet_sgd_step_f32(float* p, const float* g, float* buf, const float* hyper5, long n, cenet_stream_t stream);
 /* torch.optim.Adam / AdamW (amsgrad off) over a flat arena, one pass; exp_avg / exp_avg_sq are the flat fp32 moment buffers.
@@ -724,6 +757,13 @@ int cenet_seg_loss_ex_fwd_bf16(const unsigned short* logits, const float* labels
 int cenet_seg_loss_ex_bwd_bf16(const unsigned short* logits, const float* labels, const float* cw, const float* ws, const float*
     gout, unsigned short* dlogits, int B, int K, int H, int W, float w_dice, float w_ce, float w_bd, float w_jac, float smooth,
     int has_ignore, int ignore_index, int from_probs, cenet_stream_t stream);
+/* edt.hip, dist_loss.hip */
+int cenet_dist_maps_logits_bf16(const unsigned short* logits, int* ws, long ws_ints, int* d2, int B, int K, int H, int W,
+    cenet_stream_t stream);
+int cenet_dist_loss_fwd_bf16(const unsigned short* logits, const float* labels, const int* d2g, const int* d2p, const float* w,
+    float* ws, long ws_floats, float* loss, int B, int K, int H, int W, int surface, int hausdorff, cenet_stream_t stream);
+int cenet_dist_loss_bwd_bf16(const unsigned short* logits, const float* labels, const int* d2g, const int* d2p, const float* w,
+    const float* gout, unsigned short* dlogits, int B, int K, int H, int W, int surface, int hausdorff, cenet_stream_t stream);
 /* norm.hip */
 int cenet_layernorm_fwd_bf16(const unsigned short* x, const float* gamma, const float* beta, unsigned short* y, float* mean,
     float* rstd, int rows, int C, float eps, cenet_stream_t stream);
