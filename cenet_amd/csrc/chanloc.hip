@@ -43,6 +43,14 @@ __device__ __forceinline__ void block_sum_n(float (&v)[N], float* red) {
   }
 }
 
+// Shift of a one-pass variance: BatchNorm's batch variance is formed as s2 / n - (s1 / n)^2 from sums of (x - K) and (x - K)^2,
+// which is only as good as K is close to the mean.  K is the mean of the first min(HW, 64) values of image 0's plane (as
+// norm.hip's bn_shift_block: NOT one sample, a single outlier there cost the variance 1e-3 of its value), one sample per
+// lane, taken by EVERY wave for itself: no barrier, the same value in every thread.  v: the lane's sample; m: samples.
+__device__ __forceinline__ float shift_mean(float v, int m) {
+  return wave_sum_dpp(((int)threadIdx.x & 63) < m ? v : 0.f) / (float)m;
+}
+
 // Strided walks without a division per element: thread t visits e = t, t + NT, ... of a [B][HW] (or [B][H][W]) index space and
 // keeps (b, p) / (b, i, j) up to date with adds and carries (an integer division by a run-time value is ~40 instructions: more
 // than the arithmetic of any element here).
@@ -191,11 +199,16 @@ __global__ __launch_bounds__(NT) void eucb_fwd_kernel(EucbArgs a) {
     eucb_combine(w, q);
   }
   __syncthreads();
-  // pass 1: batch statistics of the conv output (shifted by the value at the plane centre of image 0: fp32 sums of squares)
+  // pass 1: batch statistics of the conv output (fp32 sums of squares, shifted by the mean of the quads of image 0's first
+  // min(HW, 64) source pixels: shift_mean)
   float S[3][3], u[2][2];
-  eucb_load_nb(xs, 0, H / 2, W / 2, H, W, S);
-  eucb_quad(S, q, u);
-  const float K = u[0][0];
+  const int ms = HW < 64 ? HW : 64;
+  {
+    const int ps = ((int)threadIdx.x & 63) < ms ? ((int)threadIdx.x & 63) : 0;
+    eucb_load_nb(xs, 0, ps / W, ps % W, H, W, S);
+    eucb_quad(S, q, u);
+  }
+  const float K = shift_mean(0.25f * ((u[0][0] + u[0][1]) + (u[1][0] + u[1][1])), ms);
   float s[2] = {0.f, 0.f};
   Walk3 wk(threadIdx.x, NT, H, W);
   for (int e = threadIdx.x; e < items; e += NT, wk.next()) {
@@ -464,13 +477,6 @@ __device__ __forceinline__ float round_to(float v) {
 // w holds images w, w + nw, ... (slot s), lane l the pixels l, l + 64, ... (row r) — so that per-image reductions are shuffle
 // trees inside one wave and batch reductions one LDS round.  Element k of a thread = (slot k / Rr, row k % Rr), Rr = ceil(HW / 64);
 // slot and row advance with scalar adds under full unrolling.  The host picks EPT >= slots * Rr.
-__device__ __forceinline__ float own_lane0(float v) {  // lane 0's value in every lane
-#ifdef CENET_HOSTSIM_BUILD
-  return __shfl(v, 0);
-#else
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-#endif
-}
 struct Own {
   int lane, wave, nw, Rr, B, HW;
   __device__ __forceinline__ Own(int B_, int HW_) : B(B_), HW(HW_) {
@@ -516,7 +522,10 @@ __global__ __launch_bounds__(1024) void cfam_mid_fwd_kernel(MidArgs a) {
     M[k] = ldf(mm + q);
     X[k] = ldf(x0 + q);
   })
-  const float KP = ldf(pr), KM = ldf(mm), KX = ldf(x0);  // (shifts of the sums of squares: the channel's first element)
+  // (shifts of the sums of squares, shift_mean: image 0's first min(HW, 64) elements, one per lane)
+  const int ms = HW < 64 ? HW : 64, ls_ = o.lane < ms ? o.lane : 0;
+  const float SP = ldf(pr + ls_), SM_ = ldf(mm + ls_), SX = ldf(x0 + ls_);
+  const float KP = shift_mean(SP, ms);
   const float n = (float)a.B * (float)HW, wv = a.w[0], ls = a.ls[c];
   // (every per-channel scalar is fetched HERE, with the tensor loads: a load issued after a barrier is a cold miss on the
   // critical path between two passes)
@@ -535,7 +544,7 @@ __global__ __launch_bounds__(1024) void cfam_mid_fwd_kernel(MidArgs a) {
   if (threadIdx.x == 0) bn_publish(a.meanp, a.varp, a.rmp, a.rvp, a.momp, a.nbtp, c, mup, varp, n);
   const float ap = gp_ * rsqrtf(varp + a.epsp), cp = bp_ - mup * ap;
   // x1 and its statistics (of the values as stored: the backward pass normalises what it reads)
-  const float K2 = round_to<T>(KX + ls * ((1.f - wv) * KM + wv * (ap * KP + cp)));
+  const float K2 = shift_mean(round_to<T>(SX + ls * ((1.f - wv) * SM_ + wv * (ap * SP + cp))), ms);
   s[0] = s[1] = 0.f;
   OWN_FOR(o, {
     X[k] = round_to<T>(X[k] + ls * ((1.f - wv) * M[k] + wv * (ap * P[k] + cp)));
@@ -781,7 +790,13 @@ __global__ __launch_bounds__(1024) void dwbn_fwd_kernel(DwBnArgs a) {
   for (int k = 0; k < 9; ++k) w[k] = a.w[j][cl * 9 + k];
   const float gm = a.gamma[c], bt = a.beta[c], invW = 1.f / (float)W;
   __syncthreads();
-  const float K = round_to<T>(dw_tap9(xs, H, W, H / 2, W / 2, dil, w, tap));
+  float K;  // (shift of the sums of squares, shift_mean: the stored conv output at image 0's first min(HW, 64) pixels)
+  {
+    const int ms = HW < 64 ? HW : 64;
+    int pi, pj;
+    pix_ij(o.lane < ms ? o.lane : 0, W, invW, pi, pj);
+    K = shift_mean(round_to<T>(dw_tap9(xs, H, W, pi, pj, dil, w, tap)), ms);
+  }
   float U[EPT];
   float s[2] = {0.f, 0.f};
   OWN_FOR(o, {
@@ -1238,7 +1253,8 @@ __global__ __launch_bounds__(1024) void cfam_front_fwd_kernel(FrontArgs a) {
   T *y1 = (T*)a.y1 + cb, *xs = (T*)a.xs + cb;
   float X[EPT];
   OWN_FOR(o, { X[k] = ldf(x + (ok ? b * sb + p : 0)); })
-  const float K = ldf(x);
+  const int ms = HW < 64 ? HW : 64;
+  const float K = shift_mean(ldf(x + (o.lane < ms ? o.lane : 0)), ms);  // (image 0's first min(HW, 64) elements)
   const float g1 = a.g1[c], b1 = a.b1[c];
   float w1[9], w2[3];
 #pragma unroll
@@ -1268,7 +1284,7 @@ __global__ __launch_bounds__(1024) void cfam_front_fwd_kernel(FrontArgs a) {
       q1 = q2 = 0.f;
       mx = -3.4e38f;
       mi = 0;
-      Kb = own_lane0(X[k]);  // (pixel 0 of the image: lane 0, row 0)
+      Kb = shift_mean(X[k], ms);  // (the image's first min(HW, 64) pixels: row 0 of the slot)
     }
     if (ok) {
       const float d = X[k] - Kb;
@@ -1634,12 +1650,14 @@ __global__ __launch_bounds__(256) void pool_mix_bwd_kernel(PoolArgs a) {
   T* dx = (T*)a.y + (long)b * a.syb + (long)ci * HW;
   for (int q = threadIdx.x; q < HW; q += 256) {
     const int iy = q / W, ix = q - iy * W;
-    // the bins that hold row iy: floor(iy 7 / H) and (windows overlap by at most one row) its neighbours
-    const int oy0 = (iy * POOLB) / H, ox0 = (ix * POOLB) / W;
+    // the bins that hold row iy: pool_hi(oy) > iy <=> oy >= floor(7 iy / H), pool_lo(oy) <= iy <=> oy <= ceil(7 (iy + 1) / H) - 1
+    // (two neighbours where H >= 7; below 7 the windows repeat pixels and a row sits in up to ceil(7 / H) + 1 bins)
+    const int oy0 = (iy * POOLB) / H, oy1 = (POOLB * (iy + 1) + H - 1) / H - 1;
+    const int ox0 = (ix * POOLB) / W, ox1 = (POOLB * (ix + 1) + W - 1) / W - 1;
     float sm = 0.f;
-    for (int oy = oy0 > 0 ? oy0 - 1 : 0; oy <= oy0 + 1 && oy < POOLB; ++oy) {
+    for (int oy = oy0; oy <= oy1 && oy < POOLB; ++oy) {
       if (iy < pool_lo(oy, H) || iy >= pool_hi(oy, H)) continue;
-      for (int ox = ox0 > 0 ? ox0 - 1 : 0; ox <= ox0 + 1 && ox < POOLB; ++ox)
+      for (int ox = ox0; ox <= ox1 && ox < POOLB; ++ox)
         if (ix >= pool_lo(ox, W) && ix < pool_hi(ox, W)) sm += dpl[oy * POOLB + ox];
     }
     stf(dx + q, sm);
@@ -1655,7 +1673,7 @@ __global__ __launch_bounds__(256) void pool_up_fwd_kernel(PoolArgs a) {
   __shared__ float tmp[POOLB * 64];
   const int c = blockIdx.x, b = blockIdx.y, B = a.B, P = a.P, H = a.H, W = a.W, n = B * POOLK;
   float s[2] = {0.f, 0.f};
-  const float K = a.t[(long)c * POOLK];
+  const float K = shift_mean(a.t[(long)c * POOLK + (((int)threadIdx.x & 63) < POOLK ? ((int)threadIdx.x & 63) : 0)], POOLK);  // (image 0's plane)
   for (int e = threadIdx.x; e < n; e += 256) {
     const int bb = e / POOLK, k = e - bb * POOLK;
     const float v = a.t[((long)bb * P + c) * POOLK + k] - K;

@@ -841,6 +841,12 @@ int cenet_cast_clear_bias_f32_to_bf16(float* x, unsigned short* y, const float* 
 /* ---- channel-local fused chains (chanloc.hip, round 5) --------------------------------------------------------------------
  * One workgroup owns one channel over the whole batch: BatchNorm's batch statistics are workgroup reductions, nothing is
  * stored between the steps of the chain, no float atomics (results independent of scheduling).
+ * Every batch variance here is the biased one, formed in one pass as s2 / n - (s1 / n)^2 from fp32 sums of (v - K) and (v - K)^2
+ * with the shift K = the mean of the first min(HW, 64) values of image 0's plane of the channel (not one sample: a single outlier
+ * there used to cost the variance 1e-3 of its value); it meets the two-pass bound of tests/norm_ref.py on any data whose first
+ * plane is not far from the channel's mean in units of its deviation.  Where a step's value is also an output tensor (dwbn's conv
+ * output, cfam_mid's x1 and d_x0, cfam_front's y1) the chain goes on with the value AS STORED in the tensor type, so that the
+ * backward pass, which reads or recomputes and rounds the same value, normalises what the forward normalised.
  * EUCB front, blocks.py:297-321 up to the 1x1 conv: y = LeakyReLU(BatchNorm_train(DW3x3(nearest_x2(x)))); x [B, C, H, W] (batch
  * stride sxb), y [B, C, 2H, 2W] (batch stride syb), w [C][9] (no bias).  Forward writes the batch mean / biased variance of the
  * conv output and updates the running statistics (unbiased variance; NULL: not wanted) and the batch counter.  Backward takes
@@ -865,10 +871,11 @@ int cenet_eucb_bwd_acc_bf16(const unsigned short* g, long sgb, const unsigned sh
 
 /* CFAM "mid" chain, cfam.py:368-372 around nlb.py:141-148 (p_raw = the Non-local block's output conv, m = that block's input, x0 =
  * the CFAM block's input; all [B, C, HW] contiguous):  p = BatchNorm_nl(p_raw); z = (1 - w) m + w p; x1 = x0 + ls[c] z;
- * y2 = BatchNorm_2(x1).  One launch each way (workgroup = channel over the batch; cenet_chanloc_supported(B, HW) says whether a
+ * y2 = BatchNorm_2(x1), BatchNorm_2 taking its statistics from x1 as stored (rounded to the tensor type).  One launch each way (workgroup = channel over the batch; cenet_chanloc_supported(B, HW) says whether a
  * channel is small enough).  Forward writes x1, y2, both batch means / biased variances, updates both running statistics and
  * counters (NULL: not wanted).  Backward: g_y2 and (optional) g_x1 in; d_p_raw, d_m, d_x0 out; the six parameter gradients are
- * ADDED into (dw, a scalar, with one float atomic per channel). */
+ * ADDED into (dw, a scalar, with one float atomic per channel).  d_x0 = d x1 is rounded to the tensor type once; d_m, d_p_raw and the
+ * parameter gradients are taken from that stored value. */
 int cenet_chanloc_supported(int B, int HW);
 int cenet_cfam_mid_fwd_f32(const float* p_raw, const float* m, const float* x0, float* x1, float* y2, const float* gamma_p,
                            const float* beta_p, float eps_p, float* mean_p, float* var_p, float* rmean_p, float* rvar_p,
@@ -898,6 +905,8 @@ int cenet_cfam_mid_bwd_acc_bf16(const unsigned short* g_y2, const unsigned short
  * way (workgroup = channel over the batch; cenet_chanloc_supported(B, H*W)):
  *   v[:, j*g + i] = ReLU(BatchNorm_train(DW3x3 with dilation dil[j] and weights w[j] ([g][9], no bias) of x[:, j*g + i])), j < nb <= 3;
  *   rest = x[:, nb*g : nb*g + p] (the pooled branch's slice; p may be 0).
+ * The conv output is rounded to the tensor type (as the launch chain stores it) and the statistics are those of the rounded values;
+ * the backward pass recomputes and rounds it the same way.
  * x [B, nb*g + p, H, W] (batch stride sxb), v [B, nb*g, H, W] (svb), rest [B, p, H, W] (srb); gamma / beta / mean / var / running
  * statistics cover the nb*g channels, num_batches_tracked holds nb counters (NULL: not wanted).
  * Backward: g_v, g_rest and g_add (another gradient of x, [B, nb*g + p, H, W], may be NULL) in; dx = their sum through the chain;
@@ -922,7 +931,8 @@ int cenet_dwbn_bwd_acc_bf16(const unsigned short* g_v, long sgb, const unsigned 
 
 /* CFAM front, cfam.py:366 over cfam.py:251-264, one launch each way (workgroup = channel over the batch, one wave per image for the
  * per-image statistics; cenet_chanloc_supported(B, HW), B <= 256):  y1 = BatchNorm_1(x0);  u[b, c] = [max, mean, biased std] of
- * y1[b, c];  z = fc2 . relu(fc1 u) (fc1 [C][3][3], fc2 [C][3]);  zn = BatchNorm1d_train(z) over the batch (gamma_d == NULL: zn = z,
+ * y1[b, c] as stored (the std in one pass, shifted by the mean of the plane's first min(HW, 64) values; amax: the smallest index of
+ * the maximum);  z = fc2 . relu(fc1 u) (fc1 [C][3][3], fc2 [C][3]);  zn = BatchNorm1d_train(z) over the batch (gamma_d == NULL: zn = z,
  * the reference's batch-of-one rule);  xs = y1 * sigmoid(zn).  All tensors [B, C, HW] contiguous; u [B, C, 3], amax / z / zn
  * [B, C] are saved for the backward pass.  Backward: g_xs (gradient of xs), g_y1 (of y1: the MCA shortcut; may be NULL), g_tap (of
  * x0 itself: the residual around the block; may be NULL) in, dx0 out; parameter gradients ADDED into. */
@@ -953,7 +963,13 @@ int cenet_cfam_front_bwd_acc_bf16(const unsigned short* g_xs, const unsigned sho
 /* Depthwise 3x3 (+bias) + activation with NO BatchNorm, cfam.py:150-151 (the CFAM Mlp's conv + GELU), one launch each way
  * (workgroup = channel over the batch, B*H*W <= 8192 and cenet_chanloc_supported(B, H*W)): y = act(DW3x3_dil(x) + bias); x, y
  * [B, C, H, W] contiguous, w [C][9], bias [C] or NULL.  The pre-activation is not stored; backward recomputes it from x and
- * writes dx; dw / dbias (may be NULL) are ADDED into. */
+ * writes dx; dw / dbias (may be NULL) are ADDED into.
+ * GELU is 0.5 u (1 + erf(u / sqrt 2)).  The fp32 instances evaluate it with erff / expf.  The bf16 instances use max(u, 0) - |u| h
+ * and, for the derivative, (u >= 0 ? 1 - h : h) + u phi(u), with h = erfc(|u| / sqrt 2) / 2 by Abramowitz & Stegun 7.1.26 (|error of
+ * erf| <= 1.5e-7, so 0.75e-7 on h) on the hardware reciprocal and exponential (1 ulp each; the degree-5 polynomial in t = 1 / (1 + p |u|)
+ * amplifies a relative error of t at most 5 times, h <= 1/2: below 2^-21 = 4.8e-7 in all), one exponential serving both terms:
+ *   |gelu_bf16(u) - gelu(u)| <= 6e-7 |u|,   |gelu'_bf16(u) - gelu'(u)| <= 7e-7   (u phi(u) <= 0.25 adds its exponential's 2^-23 / 4),
+ * a four-hundredth of a bf16 ulp. */
 int cenet_dwact_fwd_f32(const float* x, const float* w, const float* bias, float* y, int act, float slope, int dil, int B, int C,
                         int H, int W, cenet_stream_t stream);
 int cenet_dwact_bwd_acc_f32(const float* g, const float* x, const float* w, const float* bias, float* dx, float* dw_acc,

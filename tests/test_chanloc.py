@@ -1,4 +1,7 @@
-"""Channel-local fused chains (csrc/chanloc.hip, round 5) against the launch chains they replace.
+"""Channel-local fused chains (csrc/chanloc.hip, round 5) against the launch chains they replace: EQUIVALENCE SMOKE TESTS.  Both
+sides are code under test and the comparison is a relative L2 norm over whole tensors, so a convention error shared by both, one wrong
+border pixel or an ill-conditioned statistic passes here; the kernels are held per element to a float64 reference of what
+include/cenet_hip.h says they mean in tests/test_chanloc_bounds.py (reference: tests/chanloc_ref.py).
 
 The fused kernels keep intermediates in fp32 where the unfused chain stores them in the tensors' type, so in bf16 storage the two
 differ by bf16 rounding of the intermediates (bounded here in relative L2); in fp32 storage they agree to fp32 round-off.  The
