@@ -18,6 +18,10 @@ Round 5, the MI355X-native form of the same pipeline: `DeviceSlices` keeps the w
 resampling of a whole batch as three kernel launches (csrc/augment.hip, cenet_augment_acdc), `DeviceTrainLoader` is the
 `DataLoader(db_train, batch_size, shuffle=True)` of main_acdc.py:140 over them — same permutation from the same torch seed, same
 augmentation decisions from the same `random` / `np.random` seeds, no worker processes, no host copies of pixels.
+
+The Synapse training pipeline (src/datasets/dataset_synapse.py:86-112: imgaug SomeOf over ten augmenters, zoom, Normalize) on the
+same device-resident slices: `SegAugmenter` + `SYNAPSE_OPS` (csrc/augment_ops.hip, cenet_augment_ops), handed to
+`DeviceTrainLoader(augmenter=...)`.  The operator family and its distribution, each operator specified by scipy — not imgaug's numbers.
 """
 from __future__ import annotations
 
@@ -297,18 +301,197 @@ class DeviceAugmenter:
         return self.apply(*self.draw(indices))
 
 
+# The Synapse training pipeline's operators (dataset_synapse.py:86-97), in the reference's order, with its ranges.  (name, params):
+#   flips: `p`, the probability that a picked flip flips; noise: `scale` as the reference writes it (0.005 * 255); blur: `sigma`;
+#   contrast: alpha range and centre; scale: per-axis factor range; rotate / shear: degree ranges; grid_warp: control grid and the
+#   range of s in displacements ~ N(0, s) * side; translate: range of the fraction of each side.
+SYNAPSE_OPS = (
+    ("flip_ud", {"p": 0.5}),
+    ("flip_lr", {"p": 0.5}),
+    ("noise", {"scale": 0.005 * 255}),
+    ("blur", {"sigma": 1.0}),
+    ("contrast", {"alpha": (0.5, 1.5), "center": 0.0}),
+    ("scale", {"factor": (0.5, 2.0)}),
+    ("rotate", {"degrees": (-40.0, 40.0)}),
+    ("shear", {"degrees": (-16.0, 16.0)}),
+    ("grid_warp", {"grid": (4, 4), "scale": (0.008, 0.03)}),
+    ("translate", {"fraction": (-0.2, 0.2)}),
+)
+AUG_MAX_STAGES, AUG_MAX_RADIUS, AUG_MAX_GRID = 8, 16, 16  # cenet_augment_ops' limits (csrc/augment_ops.hip)
+
+
+def gaussian_weights(sigma: float, truncate: float = 4.0):
+    """(radius, the normalised weights at distance 0 .. radius) of scipy.ndimage.gaussian_filter1d's kernel, computed as scipy does"""
+    radius = int(truncate * float(sigma) + 0.5)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (float(sigma) * float(sigma)) * x ** 2)
+    phi = phi / phi.sum()
+    return radius, phi[radius:]
+
+
+def centred_affine(m, shape, shift=(0.0, 0.0)):
+    """(matrix, offset) of scipy.ndimage.affine_transform for the output -> input map o -> m (o - ctr) + ctr - shift about
+    ctr = ((H - 1) / 2, (W - 1) / 2), as ndimage.rotate(reshape=False) builds its own"""
+    m = np.asarray(m, dtype=np.float64).reshape(2, 2)
+    ctr = (np.asarray(shape, dtype=np.float64) - 1) / 2
+    return m, ctr - m @ ctr - np.asarray(shift, dtype=np.float64)
+
+
+class SegAugmenter:
+    """The Synapse training augmentation (dataset_synapse.py:86-112: imgaug `SomeOf((0, 4), [...ten augmenters...],
+    random_order=True)`, then zoom(order=3) / zoom(order=0) to the patch size, then Normalize) for a batch of DeviceSlices indices
+    -> {'image' [B, 1, h, w] float32, 'label' [B, h, w] float32 class ids} on the device (csrc/augment_ops.hip, then the resize of
+    csrc/augment.hip).
+
+    What this reproduces is the pipeline's operator family and its distribution — which operators, in what ranges, how many per
+    sample and in what order — with every operator specified by scipy (include/cenet_hip.h, cenet_augment_ops).  It does not
+    reproduce imgaug's numbers: imgaug's random stream and its cv2 interpolation are not pinned here.  The contrast centre 0.0 for
+    float images is imgaug's behaviour as remembered from its source: unverified.
+
+    The augmenter owns a numpy Generator (`seed`) and never touches the global `random` / `np.random` streams.  `draw` picks per
+    sample n uniformly in `some_of`, n distinct entries of `ops`, their order (random_order) and each one's parameters; the names
+    picked by the last draw are kept in `picked` (a picked flip that does not fire runs as a copy)."""
+
+    def __init__(self, slices: DeviceSlices, output_size: Sequence[int], ops=SYNAPSE_OPS, some_of=(0, 4), random_order: bool = True,
+                 normalize=None, seed=None):
+        self.slices, self.output_size = slices, (int(output_size[0]), int(output_size[1]))
+        self.ops, self.some_of, self.random_order = tuple(ops), (int(some_of[0]), int(some_of[1])), bool(random_order)
+        if not 0 <= self.some_of[0] <= self.some_of[1] <= min(len(self.ops), AUG_MAX_STAGES):
+            raise ValueError(f"some_of {some_of}: between 0 and min(len(ops), {AUG_MAX_STAGES}) ops per sample")
+        self.normalize = None if normalize is None else (float(normalize[0]), float(normalize[1]))
+        self.rng = np.random.default_rng(seed)
+        self.stride = slices.max_h * slices.max_w
+        self.picked = []
+        self._buf = {}
+
+    # ---- one drawn operator -> the kernel's ops: (kind, *parameters) ---------------------------------------------------------------
+    def _draw_op(self, name, prm, H, W):
+        rng = self.rng
+        if name in ("flip_ud", "flip_lr"):
+            return (name,) if rng.random() < prm["p"] else ("copy",)
+        if name == "noise":
+            k0, k1 = (int(v) for v in rng.integers(0, 2 ** 32, 2, dtype=np.uint64))
+            return ("noise", float(prm["scale"]), k0, k1)
+        if name == "blur":
+            return ("blur", float(prm["sigma"]))
+        if name == "contrast":
+            return ("contrast", float(rng.uniform(*prm["alpha"])), float(prm["center"]))
+        if name == "scale":  # the output is the input magnified by (sy, sx) about the centre
+            sy, sx = rng.uniform(*prm["factor"], 2)
+            return ("affine", *centred_affine([[1 / sy, 0], [0, 1 / sx]], (H, W)))
+        if name == "rotate":
+            a = np.deg2rad(rng.uniform(*prm["degrees"]))
+            return ("affine", *centred_affine([[np.cos(a), np.sin(a)], [-np.sin(a), np.cos(a)]], (H, W)))
+        if name == "shear":  # along x: the input column moves with the row
+            return ("affine", *centred_affine([[1, 0], [np.tan(np.deg2rad(rng.uniform(*prm["degrees"]))), 1]], (H, W)))
+        if name == "translate":
+            ty, tx = rng.uniform(*prm["fraction"], 2)
+            return ("affine", *centred_affine(np.eye(2), (H, W), shift=(ty * H, tx * W)))
+        if name == "grid_warp":
+            R, C = prm["grid"]
+            s = rng.uniform(*prm["scale"])
+            return ("grid_warp", rng.normal(0.0, s, (R, C)) * H, rng.normal(0.0, s, (R, C)) * W)
+        raise ValueError(f"SegAugmenter: unknown op {name!r}")
+
+    def plan(self, indices: Sequence[int], chains: Sequence[Sequence[tuple]]):
+        """the (tab, dp) tables of cenet_augment_ops for explicit per-sample chains of kernel ops: ('copy',), ('flip_ud',),
+        ('flip_lr',), ('affine', M [2, 2], offset [2]), ('grid_warp', dY [R, C], dX [R, C]), ('blur', sigma),
+        ('noise', scale, key0, key1), ('contrast', alpha, centre); shorter chains end in copies"""
+        from .kern import AUG_OPS, AUG_OPS_DP
+        S = max(1, max((len(c) for c in chains), default=0))
+        tab = np.zeros((len(indices), 3 + S), dtype=np.int64)
+        dp = np.zeros((len(indices), S, AUG_OPS_DP), dtype=np.float64)
+        for n, (idx, chain) in enumerate(zip(indices, chains)):
+            tab[n, :3] = (self.slices.offsets[idx], *self.slices.shapes[idx])
+            for s, (kind, *a) in enumerate(chain):
+                word, row = AUG_OPS[kind], dp[n, s]
+                if kind == "affine":
+                    row[0:4], row[4:6] = np.asarray(a[0], dtype=np.float64).reshape(-1), a[1]
+                elif kind == "grid_warp":
+                    dy, dx = (np.asarray(v, dtype=np.float64) for v in a)
+                    R, C = dy.shape
+                    assert dx.shape == (R, C) and R < 256 and C < 256
+                    word += 256 * R + 65536 * C
+                    if R * C <= AUG_MAX_GRID:  # (a larger grid is left for the library to refuse)
+                        row[:R * C], row[AUG_MAX_GRID:AUG_MAX_GRID + R * C] = dy.reshape(-1), dx.reshape(-1)
+                elif kind == "blur":
+                    radius, w = gaussian_weights(a[0])
+                    row[0] = radius
+                    if radius <= AUG_MAX_RADIUS:
+                        row[1:2 + radius] = w
+                elif kind == "noise":
+                    row[0:3] = a
+                elif kind == "contrast":
+                    row[0:2] = a
+                tab[n, 3 + s] = word
+        return tab, dp
+
+    def draw(self, indices: Sequence[int]):
+        chains, self.picked = [], []
+        for idx in indices:
+            H, W = (int(v) for v in self.slices.shapes[idx])
+            n = int(self.rng.integers(self.some_of[0], self.some_of[1] + 1))
+            pick = self.rng.choice(len(self.ops), size=n, replace=False)  # (a uniformly random n-subset in uniformly random order)
+            if not self.random_order:
+                pick = np.sort(pick)
+            self.picked.append(tuple(self.ops[i][0] for i in pick))
+            chains.append([self._draw_op(*self.ops[i], H, W) for i in pick])
+        return self.plan(indices, chains)
+
+    def apply(self, plan) -> dict:
+        from . import kern
+        tab, dp = plan
+        sl, dev = self.slices, self.slices.device
+        B, S = tab.shape[0], tab.shape[1] - 3
+        OH, OW = self.output_size
+        if self._buf.get("B", 0) < B:
+            n = B * self.stride
+            self._buf = {"B": B, "img": [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2)],
+                         "lab": [torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(2)],
+                         "stage_img": torch.empty(n, dtype=torch.float64, device=dev),
+                         "stage_lab": torch.empty(n, dtype=torch.uint8, device=dev)}
+        # the resize of RandomGenerator (cenet_augment_acdc, mode 0: no quarter turn, no rotation) with the work buffer as its pool
+        tab2 = np.zeros((B, 8), dtype=np.int64)
+        dp2 = np.zeros((B, 10), dtype=np.float64)
+        H, W = tab[:, 1], tab[:, 2]
+        tab2[:, 0], tab2[:, 1], tab2[:, 2] = np.arange(B) * self.stride, H, W
+        tab2[:, 6] = (H != OH) | (W != OW)
+        dp2[:, 6], dp2[:, 7] = _SPLINE_POLE ** (H - 1), _SPLINE_POLE ** (W - 1)
+        dp2[:, 8], dp2[:, 9] = (H - 1) / (OH - 1), (W - 1) / (OW - 1)
+        pin = dev.type == "cuda"
+        up = []
+        for a in (tab, dp, tab2, dp2):
+            t = torch.from_numpy(a)
+            up.append((t.pin_memory() if pin else t).to(dev, non_blocking=True))
+        buf = self._buf
+        r = kern.augment_ops(sl.pool_img, sl.pool_lab, tab, dp, up[0], up[1], buf["img"], buf["lab"], self.stride, sl.max_h, sl.max_w,
+                             B, S)
+        image = torch.empty(B, 1, OH, OW, dtype=torch.float32, device=dev)
+        label = torch.empty(B, OH, OW, dtype=torch.float32, device=dev)
+        kern.augment_acdc(buf["img"][r], buf["lab"][r], up[2], up[3], buf["stage_img"], buf["stage_lab"], self.stride, sl.max_h,
+                          sl.max_w, image, label, B, OH, OW)
+        if self.normalize is not None:
+            kern.augment_normalize(image, *self.normalize)
+        return {"image": image, "label": label}
+
+    def __call__(self, indices: Sequence[int]) -> dict:
+        return self.apply(self.draw(indices))
+
+
 class DeviceTrainLoader:
     """`DataLoader(db_train, batch_size=B, shuffle=True)` (main_acdc.py:140) over DeviceSlices: the index order is torch's own
     RandomSampler / BatchSampler (and one draw for the iterator's base seed, as DataLoader makes), so the same torch seed gives
     the reference's batches; every batch is {'image', 'label', 'case_name'} with the tensors already on the device."""
 
     def __init__(self, slices: DeviceSlices, output_size: Sequence[int], batch_size: int, shuffle: bool = True,
-                 drop_last: bool = False, generator: Optional[torch.Generator] = None, sampler=None):
+                 drop_last: bool = False, generator: Optional[torch.Generator] = None, sampler=None, augmenter=None):
         """sampler: an index sampler over range(len(slices)) instead of the shuffle — one process per GPU passes
         `DistributedSampler(range(len(slices)), num_replicas=world, rank=rank)` (and calls its set_epoch), exactly as with a DataLoader;
-        every rank keeps the whole set resident (0.35 GB) and augments its own shard."""
+        every rank keeps the whole set resident (0.35 GB) and augments its own shard.
+        augmenter: called with a batch's indices in place of the built-in DeviceAugmenter (a SegAugmenter over the same slices for
+        the Synapse pipeline); output_size is the built-in augmenter's and unused then."""
         from torch.utils.data import BatchSampler, RandomSampler, SequentialSampler
-        self.slices, self.aug = slices, DeviceAugmenter(slices, output_size)
+        self.slices, self.aug = slices, augmenter if augmenter is not None else DeviceAugmenter(slices, output_size)
         self.generator = generator
         src = range(len(slices))
         if sampler is None:

@@ -1297,6 +1297,38 @@ def augment_acdc(pool_img, pool_lab, tab, dp, stage_img, stage_lab, stage_stride
             B, OH, OW)
 
 
+AUG_OPS = {"copy": 0, "flip_ud": 1, "flip_lr": 2, "affine": 3, "grid_warp": 4, "blur": 5, "noise": 6, "contrast": 7}
+AUG_OPS_DP = 32  # doubles per (sample, stage) of cenet_augment_ops
+
+
+def augment_ops(pool_img, pool_lab, tab_host, dp_host, tab, dp, work_img, work_lab, stride, max_h, max_w, B, S):
+    """cenet_augment_ops (augment_ops.hip): S stages of flips / warps / blur / noise / contrast for one batch of device-resident
+    slices.  tab_host [B, 3 + S] int64 and dp_host [B, S, 32] float64 are the plan as numpy arrays, tab / dp the same tables on
+    the device; work_img / work_lab: two fp32 and two uint8 buffers of B * stride elements.  The result is in buffer S & 1."""
+    import numpy as np
+    assert tab_host.dtype == np.int64 and tab_host.shape == (B, 3 + S) and tab_host.flags.c_contiguous
+    assert dp_host.dtype == np.float64 and dp_host.shape == (B, S, AUG_OPS_DP) and dp_host.flags.c_contiguous
+    assert tab.numel() == tab_host.size and dp.numel() == dp_host.size
+    for t in (pool_img, pool_lab, tab, dp, *work_img, *work_lab):
+        assert t.is_contiguous()
+    assert all(t.numel() >= B * stride for t in (*work_img, *work_lab))
+    _launch("cenet_augment_ops", pool_img, pool_lab, tab_host.ctypes.data, dp_host.ctypes.data, tab, dp, work_img[0], work_lab[0],
+            work_img[1], work_lab[1], stride, max_h, max_w, B, S)
+    return S & 1
+
+
+def philox4x32_10(ctr_key, out):
+    """cenet_philox4x32_10: ctr_key [n, 6] int64 (4 counter + 2 key words) -> out [n, 4] int64, the generator of the noise op"""
+    assert ctr_key.is_contiguous() and out.is_contiguous() and ctr_key.shape[1] == 6 and out.shape == (ctr_key.shape[0], 4)
+    _launch("cenet_philox4x32_10", ctr_key, out, ctr_key.shape[0])
+
+
+def augment_normalize(x, mean, std):
+    """cenet_augment_normalize: x = (x - mean) / std in fp32, in place"""
+    assert x.is_contiguous()
+    _launch("cenet_augment_normalize", x, x.numel(), mean, std)
+
+
 _SPLINE_POLE = math.sqrt(3.0) - 2.0  # the cubic B-spline prefilter's pole (scipy ni_splines)
 
 

@@ -1046,6 +1046,36 @@ int cenet_augment_acdc(const float* pool_img, const unsigned char* pool_lab, con
                        unsigned char* stage_lab, long stage_stride, int max_h, int max_w, float* out_img, float* out_lab, int B,
                        int OH, int OW, cenet_stream_t stream);
 
+/* Composable slice augmentation on the device (augment_ops.hip): the operator family of the Synapse training pipeline
+ * (src/datasets/dataset_synapse.py:86-112), each operator specified by scipy, up to S <= 8 stages per sample for a whole batch.
+ * The operators and their distribution are the pipeline's; imgaug's random stream and interpolation bits are not claimed.
+ *   tab[(3 + S) b ..]       = offset (elements into the pools), H, W, then S op words
+ *   dp[32 (S b + s) ..]     = the parameter row of stage s of sample b, computed by the host in fp64
+ *   op word                   image (fp32 in, fp64 arithmetic without contraction, fp32 out)            label (uint8)    dp row
+ *   0 copy                    v                                                                          same             -
+ *   1 flip_ud / 2 flip_lr     index map                                                                  same map         -
+ *   3 affine                  scipy.ndimage.affine_transform(a64, M, offset, order=1, mode="constant")   order=0          M00 M01 M10 M11 off0 off1
+ *   4 + 256 R + 65536 C       map_coordinates(order=1, mode="constant") at (i + dY, j + dX), dY / dX     order=0          dY[R*C] at 0, dX[R*C] at 16
+ *     grid_warp               the bilinear samples of R x C control grids at (i (R-1)/(H-1), j (C-1)/(W-1))
+ *   5 blur                    gaussian_filter(a64, sigma, mode="mirror"), axis 0 then axis 1             unchanged        radius, w[0 .. radius]
+ *   6 noise                   v + scale * z(p): Philox4x32-10, counter (p, 0, 0, 0), p = i W + j,        unchanged        scale, key0, key1
+ *                             z = sqrt(-2 ln u1) cos(2 pi u2), u = (word + 0.5) / 2^32 of output words 0, 1
+ *   7 contrast                c + alpha * (v - c)                                                        unchanged        alpha, c
+ * (blur: w[0] the centre weight and w[k] the normalised weight of both taps at distance k.)  Stage s reads the pools (s = 0) or
+ * work buffer s & 1 and writes work buffer (s + 1) & 1: the result, sample b at b * stride with its own H x W, is in buffer S & 1.
+ * Both work buffers hold B * stride fp32 and B * stride uint8.  tab_host / dp_host are the tables in host memory, tab / dp the
+ * same tables on the device: the host copies are checked before anything is launched.  CENET_EINVAL (nothing launched) for an
+ * unknown op word, S < 1 or S > 8, a blur radius above 16, R < 2, C < 2 or R*C > 16, H > max_h, W > max_w, H*W > stride or
+ * B > 65535. */
+int cenet_augment_ops(const float* pool_img, const unsigned char* pool_lab, const long* tab_host, const double* dp_host,
+                      const long* tab, const double* dp, float* work_img0, unsigned char* work_lab0, float* work_img1,
+                      unsigned char* work_lab1, long stride, int max_h, int max_w, int B, int S, cenet_stream_t stream);
+/* Philox4x32-10 as cenet_augment_ops draws it, for n rows of ctr_key [n, 6] = 4 counter and 2 key words (each 0 .. 2^32 - 1,
+ * held as long) -> out [n, 4] output words: holds the generator to the published Random123 vectors. */
+int cenet_philox4x32_10(const long* ctr_key, long* out, int n, cenet_stream_t stream);
+/* x[0 .. n) = (x - mean) / std in fp32, in place: Normalize([mean], [std]) after the augmentation's resize. */
+int cenet_augment_normalize(float* x, long n, float mean, float std, cenet_stream_t stream);
+
 /* Test-time volume inference on the device (volresize.hip; src/utils/metrics_eval.py:37-84, utils_synapse.py:49-97).
  * cenet_vol_resize_cubic: scipy.ndimage.zoom(slice, (PH / H, PW / W), order=3) for n slices src [n, H, W] fp32 -> out
  * [n, 1, PH, PW] fp32, computed in fp64 in scipy's operation order (prefilter with mirror boundary along axis 0 then axis 1,
