@@ -25,30 +25,11 @@
 // there.  No atomics: two runs are bit-identical.
 #include "common.h"
 #include "../../include/cenet_hip.h"
-#include "spline3.h"  // aug_mirror; fp contraction off from here on
+#include "augment_ops.h"  // Philox, the tap order; fp contraction off from here on
 
-#define AOP_MAX_STAGES 8
-#define AOP_DP 32      // doubles per (sample, stage)
-#define AOP_MAX_RADIUS 16
 #define AOP_MAX_GRID 16
-#define AOP_TH 8
-#define AOP_TW 32
 
 enum { AOP_COPY = 0, AOP_FLIP_UD, AOP_FLIP_LR, AOP_AFFINE, AOP_GRID_WARP, AOP_BLUR, AOP_NOISE, AOP_CONTRAST, AOP_COUNT };
-
-// Philox4x32-10 (Salmon et al., SC'11; Random123): ten rounds, the key bumped by the Weyl constants between them
-__host__ __device__ __forceinline__ void aop_philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1;
-    c[0] = n0;
-    c[1] = (unsigned)p1;
-    c[2] = n2;
-    c[3] = (unsigned)p0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
 
 // one standard normal per pixel: counter (p, 0, 0, 0), Box-Muller on the first two output words
 __device__ __forceinline__ double aop_normal(unsigned p, unsigned k0, unsigned k1) {
@@ -87,11 +68,6 @@ __device__ __forceinline__ double aop_grid_at(const double* __restrict__ D, int 
   const double* a = D + r0 * C + c0;
   return (1.0 - fy) * ((1.0 - fx) * a[0] + fx * a[1]) + fy * ((1.0 - fx) * a[C] + fx * a[C + 1]);
 }
-
-// one line of scipy's correlate1d with a symmetric kernel: centre first, then the pairs from the outermost inwards
-#define AOP_SYMMETRIC_TAPS(AT)                                                  \
-  double acc = (AT(0)) * w[0];                                                  \
-  for (int ii = radius; ii > 0; --ii) acc += ((AT(-ii)) + (AT(ii))) * w[ii];
 
 // grid (tiles, B)
 __global__ __launch_bounds__(256) void aug_ops_stage_kernel(const float* __restrict__ src_img, const unsigned char* __restrict__ src_lab,

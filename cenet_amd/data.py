@@ -478,6 +478,198 @@ class SegAugmenter:
         return self.apply(self.draw(indices))
 
 
+class DeviceImages:
+    """All (image [C, H, W] float32 — channels first, planar; 1 <= C <= 4 —, label [H, W] class ids) training samples of ONE
+    shape, packed into two device pools: sample n's channels at pool_img[n * C * H * W], its label at pool_lab[n * H * W].
+    (A channels-last [H, W, C] image is NOT accepted: with H or W <= 4 the two layouts cannot be told apart; `from_arrays` takes
+    the reference's files.)"""
+
+    def __init__(self, samples: Sequence, device, names: Optional[Sequence[str]] = None):
+        imgs, labs = [], []
+        for img, lab in samples:
+            img, lab = np.asarray(img), np.asarray(lab)
+            assert img.ndim == 3 and img.shape[1:] == lab.shape, (img.shape, lab.shape)
+            assert lab.min() >= 0 and lab.max() < 256, "labels are class ids"
+            imgs.append(np.ascontiguousarray(img, dtype=np.float32))
+            labs.append(np.ascontiguousarray(lab).astype(np.uint8))
+        assert imgs and all(a.shape == imgs[0].shape for a in imgs), "all samples share one shape"
+        self.channels, self.height, self.width = (int(v) for v in imgs[0].shape)
+        assert 1 <= self.channels <= 4, self.channels
+        self.device = torch.device(device)
+        self.pool_img = torch.from_numpy(np.stack(imgs).reshape(-1)).to(self.device)
+        self.pool_lab = torch.from_numpy(np.stack(labs).reshape(-1)).to(self.device)
+        self.count = len(imgs)
+        self.names = list(names) if names is not None else None
+
+    @classmethod
+    def from_arrays(cls, X, Y, device, names: Optional[Sequence[str]] = None):
+        """the reference's X_tr_*.npy [N, C, H, W] in [0, 1] and Y_tr_*.npy [N, 1, H, W] (or [N, H, W]) in [0, 1]
+        (dataset_ham.py:78-79): images become uint8(x * 255) held as float32 in [0, 255], masks class id 1 where uint8(y * 255) >=
+        128 and 0 elsewhere (what the reference's per-sample min-max makes of a 0 / 255 mask)"""
+        X, Y = np.asarray(X), np.asarray(Y)
+        Y = Y[:, 0] if Y.ndim == 4 else Y
+        assert X.ndim == 4 and Y.shape == (X.shape[0], *X.shape[2:]), (X.shape, Y.shape)
+        return cls([(np.uint8(x * 255).astype(np.float32), (np.uint8(y * 255) >= 128).astype(np.uint8)) for x, y in zip(X, Y)],
+                   device, names=names)
+
+    def __len__(self):
+        return self.count
+
+
+# The skin training pipeline's transforms (dataset_ham.py:273-281, dataset_ph2.py:250-257: albumentations Compose), in the
+# reference's order, each with its own probability `p` and its ranges.  (name, params):
+#   rotate: degree range, border 'mirror' (albumentations' default BORDER_REFLECT_101 is scipy's 'mirror'); flips: `p` only;
+#   brightness_contrast: alpha = 1 + U(contrast), beta = max_value * U(brightness), clipped to [0, max_value] — contrast_limit =
+#   brightness_limit = 0.2 and brightness_by_max on uint8 are albumentations' defaults as remembered from its source: unverified;
+#   blur: odd kernel sizes k, sigma = 0.3 * ((k - 1) * 0.5 - 1) + 0.8 (cv2.getGaussianKernel's rule for sigma = 0), radius
+#   (k - 1) / 2, weights normalised; elastic: displacement = alpha * gaussian_filter(uniform(-1, 1), sigma, truncate), border 'mirror'.
+SKIN_OPS = (
+    ("rotate", {"p": 0.5, "degrees": (-30.0, 30.0), "mode": "mirror"}),
+    ("flip_lr", {"p": 0.5}),
+    ("flip_ud", {"p": 0.5}),
+    ("brightness_contrast", {"p": 0.2, "contrast": (-0.2, 0.2), "brightness": (-0.2, 0.2), "max_value": 255.0}),
+    ("blur", {"p": 0.3, "kernel": (3, 5, 7)}),
+    ("elastic", {"p": 0.3, "alpha": 1.0, "sigma": 50.0, "truncate": 4.0, "mode": "mirror"}),
+)
+AUG_MAX_FIELD_RADIUS = 256  # cenet_augment_image_ops' limit (csrc/augment_image_ops.hip)
+
+
+def blur_weights(k: int):
+    """(radius, the normalised weights at distance 0 .. radius) of a k-tap Gaussian with cv2's sigma for a kernel size"""
+    radius = (int(k) - 1) // 2
+    sigma = 0.3 * ((int(k) - 1) * 0.5 - 1) + 0.8
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return radius, phi[radius:]
+
+
+class ComposeAugmenter:
+    """The skin training augmentation (dataset_ham.py:273-281 / dataset_ph2.py:250-257: albumentations `Compose([Rotate(limit=30,
+    p=0.5), HorizontalFlip(p=0.5), VerticalFlip(p=0.5), RandomBrightnessContrast(p=0.2), GaussianBlur(blur_limit=(3, 7), p=0.3),
+    ElasticTransform(alpha=1, sigma=50, p=0.3)])`, then the per-sample min-max of :113) for a batch of DeviceImages indices ->
+    {'image' [B, C, H, W] float32, 'label' [B, H, W] float32 class ids} on the device (csrc/augment_image_ops.hip).
+
+    What this reproduces is the pipeline's operator family and its distribution — which operators, in what ranges, each with its
+    own probability, in the reference's order — with every operator specified by scipy (include/cenet_hip.h,
+    cenet_augment_image_ops).  It does not reproduce albumentations' numbers: albumentations' random stream, its cv2 interpolation
+    and its uint8 LUT rounding are not pinned here.  The brightness / contrast limits 0.2 and the scaling of the brightness term
+    by 255 for uint8 images are albumentations' defaults as remembered from its source: unverified.
+
+    The augmenter owns a numpy Generator (`seed`) and never touches the global `random` / `np.random` streams.  `draw` walks
+    `ops` in order for every sample, each op fires with its own `p` and draws its parameters; the names that fired in the last draw
+    are kept in `picked`.  All elastic ops of `ops` share one (sigma, truncate): the field kernel is one per call."""
+
+    def __init__(self, images: DeviceImages, ops=SKIN_OPS, minmax: bool = True, seed=None):
+        self.images, self.ops, self.minmax = images, tuple(ops), bool(minmax)
+        if len(self.ops) > AUG_MAX_STAGES:
+            raise ValueError(f"ComposeAugmenter: at most {AUG_MAX_STAGES} ops per sample")
+        fields = {(float(p["sigma"]), float(p.get("truncate", 4.0))) for n, p in self.ops if n == "elastic"}
+        if len(fields) > 1:
+            raise ValueError("ComposeAugmenter: one (sigma, truncate) for all elastic ops")
+        self.field = fields.pop() if fields else None
+        self.rng = np.random.default_rng(seed)
+        self.picked = []
+        self._buf = {}
+
+    # ---- one fired transform -> the kernel's op: (kind, *parameters) -----------------------------------------------------------------
+    def _draw_op(self, name, prm):
+        rng, H, W = self.rng, self.images.height, self.images.width
+        if name in ("flip_ud", "flip_lr"):
+            return (name,)
+        if name == "rotate":
+            a = np.deg2rad(rng.uniform(*prm["degrees"]))
+            return ("affine", *centred_affine([[np.cos(a), np.sin(a)], [-np.sin(a), np.cos(a)]], (H, W)), prm.get("mode", "constant"))
+        if name == "brightness_contrast":
+            alpha, beta = 1.0 + rng.uniform(*prm["contrast"]), prm["max_value"] * rng.uniform(*prm["brightness"])
+            return ("brightness_contrast", float(alpha), float(beta), 0.0, float(prm["max_value"]))
+        if name == "blur":
+            return ("blur", int(rng.choice(prm["kernel"])))
+        if name == "elastic":
+            k0, k1 = (int(v) for v in rng.integers(0, 2 ** 32, 2, dtype=np.uint64))
+            return ("elastic", float(prm["alpha"]), k0, k1, prm.get("mode", "constant"))
+        raise ValueError(f"ComposeAugmenter: unknown op {name!r}")
+
+    def plan(self, indices: Sequence[int], chains: Sequence[Sequence[tuple]], field=None):
+        """the (tab, dp, fw) tables of cenet_augment_image_ops for explicit per-sample chains of kernel ops: ('copy',),
+        ('flip_ud',), ('flip_lr',), ('affine', M [2, 2], offset [2], mode), ('blur', k) or ('blur', weights [radius + 1]),
+        ('brightness_contrast', alpha, beta, lo, hi), ('elastic', alpha, key0, key1, mode); mode 'constant' / 'mirror'; shorter
+        chains end in copies.  field: (sigma, truncate) of the elastic kernel (default: the augmenter's own); fw is its
+        gaussian_weights [radius + 1], or None when no chain is elastic"""
+        from .kern import AUG_IMAGE_MIRROR, AUG_IMAGE_OPS, AUG_OPS_DP
+        S = max(1, max((len(c) for c in chains), default=0))
+        tab = np.zeros((len(indices), 1 + S), dtype=np.int64)
+        dp = np.zeros((len(indices), S, AUG_OPS_DP), dtype=np.float64)
+        elastic = False
+        for n, (idx, chain) in enumerate(zip(indices, chains)):
+            tab[n, 0] = idx
+            for s, (kind, *a) in enumerate(chain):
+                word, row = AUG_IMAGE_OPS[kind], dp[n, s]
+                if kind == "affine":
+                    row[0:4], row[4:6] = np.asarray(a[0], dtype=np.float64).reshape(-1), a[1]
+                elif kind == "blur":
+                    radius, w = blur_weights(a[0]) if np.ndim(a[0]) == 0 else (len(a[0]) - 1, np.asarray(a[0], dtype=np.float64))
+                    row[0] = radius
+                    if radius <= AUG_MAX_RADIUS:  # (a larger one is left for the library to refuse)
+                        row[1:2 + radius] = w
+                elif kind == "brightness_contrast":
+                    row[0:4] = a
+                elif kind == "elastic":
+                    row[0:3] = a[0:3]
+                    elastic = True
+                if kind in ("affine", "elastic"):
+                    mode = a[-1]
+                    assert mode in ("constant", "mirror"), mode
+                    word += AUG_IMAGE_MIRROR * (mode == "mirror")
+                tab[n, 1 + s] = word
+        fw = None
+        if elastic:
+            field = self.field if field is None else field
+            assert field is not None, "an elastic op needs the field's (sigma, truncate)"
+            fw = np.ascontiguousarray(gaussian_weights(*field)[1])
+        return tab, dp, fw
+
+    def draw(self, indices: Sequence[int]):
+        chains, self.picked = [], []
+        for _ in indices:
+            fired = [(n, p) for n, p in self.ops if self.rng.random() < p["p"]]
+            self.picked.append(tuple(n for n, _ in fired))
+            chains.append([self._draw_op(n, p) for n, p in fired])
+        return self.plan(indices, chains)
+
+    def apply(self, plan) -> dict:
+        from . import kern
+        tab, dp, fw = plan
+        im, dev = self.images, self.images.device
+        B, S = tab.shape[0], tab.shape[1] - 1
+        C, H, W = im.channels, im.height, im.width
+        n = C * H * W
+        if self._buf.get("B", 0) < B:
+            self._buf = {"B": B, "img": [torch.empty(B * n, dtype=torch.float32, device=dev) for _ in range(2)],
+                         "lab": [torch.empty(B * H * W, dtype=torch.uint8, device=dev) for _ in range(2)],
+                         "part": torch.empty(B * 2 * kern.AUG_MINMAX_PARTS, dtype=torch.float32, device=dev), "field": None}
+        buf = self._buf
+        if fw is not None and buf["field"] is None:
+            buf["field"] = torch.empty(buf["B"] * 2 * H * W, dtype=torch.float64, device=dev)
+        pin = dev.type == "cuda"
+        up = []
+        for a in (tab, dp, fw):
+            t = None if a is None else torch.from_numpy(a)
+            up.append(None if t is None else (t.pin_memory() if pin else t).to(dev, non_blocking=True))
+        label = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+        r = kern.augment_image_ops(im.pool_img, im.pool_lab, tab, dp, up[0], up[1], fw, up[2], buf["field"] if fw is not None else None,
+                                   buf["img"], buf["lab"], label, len(im), C, H, W, B, S)
+        if self.minmax:
+            image = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
+            kern.augment_minmax(buf["img"][r], image, buf["part"], B, n)
+        else:
+            image = buf["img"][r][:B * n].view(B, C, H, W).clone()
+        return {"image": image, "label": label}
+
+    def __call__(self, indices: Sequence[int]) -> dict:
+        return self.apply(self.draw(indices))
+
+
 class DeviceTrainLoader:
     """`DataLoader(db_train, batch_size=B, shuffle=True)` (main_acdc.py:140) over DeviceSlices: the index order is torch's own
     RandomSampler / BatchSampler (and one draw for the iterator's base seed, as DataLoader makes), so the same torch seed gives
@@ -489,7 +681,8 @@ class DeviceTrainLoader:
         `DistributedSampler(range(len(slices)), num_replicas=world, rank=rank)` (and calls its set_epoch), exactly as with a DataLoader;
         every rank keeps the whole set resident (0.35 GB) and augments its own shard.
         augmenter: called with a batch's indices in place of the built-in DeviceAugmenter (a SegAugmenter over the same slices for
-        the Synapse pipeline); output_size is the built-in augmenter's and unused then."""
+        the Synapse pipeline; a ComposeAugmenter over DeviceImages, passed as `slices`, for the skin pipeline); output_size is the
+        built-in augmenter's and unused then."""
         from torch.utils.data import BatchSampler, RandomSampler, SequentialSampler
         self.slices, self.aug = slices, augmenter if augmenter is not None else DeviceAugmenter(slices, output_size)
         self.generator = generator

@@ -1329,6 +1329,46 @@ def augment_normalize(x, mean, std):
     _launch("cenet_augment_normalize", x, x.numel(), mean, std)
 
 
+AUG_IMAGE_OPS = {"copy": 0, "flip_ud": 1, "flip_lr": 2, "affine": 3, "blur": 4, "brightness_contrast": 5, "elastic": 6}
+AUG_IMAGE_MIRROR = 256  # bit 8 of an affine / elastic op word: mode='mirror' instead of 'constant'
+AUG_MINMAX_PARTS = 128  # workgroups per sample of cenet_augment_minmax
+
+
+def augment_image_ops(pool_img, pool_lab, tab_host, dp_host, tab, dp, fw_host, fw, field, work_img, work_lab, out_lab, N, C, H, W,
+                      B, S):
+    """cenet_augment_image_ops (augment_image_ops.hip): S stages of flips / affine / blur / brightness-contrast / elastic warp for
+    one batch of device-resident C-channel images.  tab_host [B, 1 + S] int64 and dp_host [B, S, 32] float64 are the plan as numpy
+    arrays, tab / dp the same tables on the device; fw_host (numpy float64 [radius + 1]) / fw: the elastic field's kernel, field:
+    B * 2 * H * W float64 of scratch (all three None when no chain is elastic); work_img / work_lab: two fp32 buffers of
+    B * C * H * W and two uint8 buffers of B * H * W elements; out_lab: None or [B, H, W] fp32.  The result is in buffer S & 1."""
+    import numpy as np
+    assert tab_host.dtype == np.int64 and tab_host.shape == (B, 1 + S) and tab_host.flags.c_contiguous
+    assert dp_host.dtype == np.float64 and dp_host.shape == (B, S, AUG_OPS_DP) and dp_host.flags.c_contiguous
+    assert tab.numel() == tab_host.size and dp.numel() == dp_host.size
+    radius = 0
+    if fw_host is not None:
+        assert fw_host.dtype == np.float64 and fw_host.ndim == 1 and fw_host.flags.c_contiguous and fw.numel() == fw_host.size
+        assert field.numel() >= B * 2 * H * W
+        radius = fw_host.size - 1
+    for t in (pool_img, pool_lab, tab, dp, fw, field, *work_img, *work_lab, out_lab):
+        assert t is None or t.is_contiguous()
+    assert pool_img.numel() >= N * C * H * W and pool_lab.numel() >= N * H * W
+    assert all(t.numel() >= B * C * H * W for t in work_img) and all(t.numel() >= B * H * W for t in work_lab)
+    assert out_lab is None or out_lab.numel() == B * H * W
+    _launch("cenet_augment_image_ops", pool_img, pool_lab, tab_host.ctypes.data, dp_host.ctypes.data, tab, dp,
+            None if fw_host is None else fw_host.ctypes.data, fw, radius, field, work_img[0], work_lab[0], work_img[1], work_lab[1],
+            out_lab, N, C, H, W, B, S)
+    return S & 1
+
+
+def augment_minmax(x, y, part, B, n):
+    """cenet_augment_minmax: y[b] = (x[b] - min) / ((max - min) + 1e-8f) per sample of x [B, n] fp32, in float32 (y may be x);
+    part: B * 2 * AUG_MINMAX_PARTS floats of scratch"""
+    assert x.is_contiguous() and y.is_contiguous() and part.is_contiguous()
+    assert x.numel() >= B * n and y.numel() >= B * n and part.numel() >= B * 2 * AUG_MINMAX_PARTS
+    _launch("cenet_augment_minmax", x, y, part, B, n)
+
+
 _SPLINE_POLE = math.sqrt(3.0) - 2.0  # the cubic B-spline prefilter's pole (scipy ni_splines)
 
 

@@ -49,7 +49,7 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
                test_volumes: Optional[Callable[[], Iterable]] = None, save_dir: Optional[str] = None, img_size: int = 224,
                test_resize: str = "device", dice_class_weights=None, ce_class_weights=None, ignore_index=None,
                test_postprocess=None, dist_weight_schedule: Optional[Callable[[int], tuple]] = None) -> dict:
-    """main_acdc.py:200-290.  tr_loader yields {'image' [B,1,H,W] float, 'label' [B,H,W]} batches (host or device tensors);
+    """main_acdc.py:200-290.  tr_loader yields {'image' [B,C,H,W] float (C = the network's input channels), 'label' [B,H,W]} batches (host or device tensors);
     val_batches() yields (image [1,1,H,W], label [1,H,W]) pairs for the per-epoch validation (main_acdc.py:218-231).
     optimizer / scheduler: the reference's --optimizer / --scheduler strings (main_acdc.py:34-35, core.py:12-41); `momentum`
     applies to SGD, Adam / AdamW take betas (0.9, 0.999) and eps 1e-8 as the reference does.

@@ -1076,6 +1076,44 @@ int cenet_philox4x32_10(const long* ctr_key, long* out, int n, cenet_stream_t st
 /* x[0 .. n) = (x - mean) / std in fp32, in place: Normalize([mean], [std]) after the augmentation's resize. */
 int cenet_augment_normalize(float* x, long n, float mean, float std, cenet_stream_t stream);
 
+/* Composable augmentation of multi-channel images on the device (augment_image_ops.hip): the operator family of the skin training
+ * pipeline (src/datasets/skin/dataset_ham.py:273-281, albumentations Compose), each operator specified by scipy / numpy, up to
+ * S <= 8 stages per sample for a batch of B samples.  The operators and their distribution are the pipeline's; albumentations'
+ * random stream, its cv2 interpolation and its uint8 LUT rounding are not claimed.  The pools hold N samples of one size: sample
+ * n's C planar channels (1 <= C <= 4) at pool_img + n*C*H*W, its label plane at pool_lab + n*H*W; H, W <= 1024.
+ *   tab[(1 + S) b ..]       = sample index n, then S op words
+ *   dp[32 (S b + s) ..]     = the parameter row of stage s of sample b, computed by the host in fp64
+ *   op word                   image, every channel (fp32 in, fp64 arithmetic without contraction, fp32 out)   label (uint8)  dp row
+ *   0 copy                    v                                                                                same           -
+ *   1 flip_ud                 a[H-1-i][j]                                                                      same map       -
+ *   2 flip_lr                 a[i][W-1-j]                                                                      same map       -
+ *   3 | m affine              affine_transform(a64, M, offset, order=1, mode=m, cval=0)                        order=0        M[4], offset[2]
+ *   4 blur                    correlate1d(correlate1d(a64, w, 0, mode='mirror'), w, 1, mode='mirror')          unchanged      radius, w[0 .. radius]
+ *   5 brightness_contrast     np.clip(alpha * a64 + beta, lo, hi)                                              unchanged      alpha, beta, lo, hi
+ *   6 | m elastic             map_coordinates(a64, [i + alpha g[0], j + alpha g[1]], order=1, mode=m, cval=0)  order=0        alpha, key0, key1
+ * m: 0 for mode='constant', 256 (bit 8) for mode='mirror'.  (blur: w[0] the centre weight and w[k] the weight of both taps at
+ * distance k.)  The elastic field g is made on the device, p = i*W + j, f = 0 (rows) / 1 (columns):
+ *   u[f][i][j] = (philox4x32_10(counter (p, f, 0, 0), key (key0, key1))[0] + 0.5) / 2^31 - 1
+ *   g[f]       = correlate1d(correlate1d(u[f], fw, 0, mode='constant', cval=0), fw, 1, mode='constant', cval=0)
+ * fw: ONE symmetric kernel per call, fw[0] the centre and fw[k] the weight of both taps at distance k <= field_radius <= 256;
+ * field: B*2*H*W doubles of scratch, g of sample b at field + b*2*H*W afterwards.  fw, fw_host and field may be null when no sample
+ * carries an elastic stage; at most one elastic stage per sample.  Stage s reads the pools (s = 0) or work buffer s & 1 and writes
+ * work buffer (s + 1) & 1: the result, sample b's channels at b*C*H*W and its label at b*H*W, is in buffer S & 1.  Both work
+ * buffers hold B*C*H*W fp32 and B*H*W uint8.  out_lab (or null): [B, H, W] fp32, the result's labels as float class ids.
+ * tab_host / dp_host / fw_host are the tables in host memory, tab / dp / fw the same on the device: the host copies are checked
+ * before anything is launched.  CENET_EINVAL (nothing launched) for an unknown op, stray bits in an op word (bit 8 on an op that
+ * takes no mode included), S < 1 or S > 8, C outside 1..4, H or W outside 1..1024, a blur radius above 16 or not an integer, a
+ * field radius above 256, a second elastic stage in one chain, a key word outside [0, 2^32), lo > hi, a sample index outside
+ * [0, N) or B > 65535. */
+int cenet_augment_image_ops(const float* pool_img, const unsigned char* pool_lab, const long* tab_host, const double* dp_host,
+                            const long* tab, const double* dp, const double* fw_host, const double* fw, int field_radius,
+                            double* field, float* work_img0, unsigned char* work_lab0, float* work_img1, unsigned char* work_lab1,
+                            float* out_lab, int N, int C, int H, int W, int B, int S, cenet_stream_t stream);
+/* Per-sample min-max normalisation (dataset_ham.py:113 on float32 arrays): y[b][i] = (x[b][i] - mn_b) / ((mx_b - mn_b) + 1e-8f)
+ * for x, y [B, n] fp32 (y may be x), all in float32.  Two launches, no atomics: per-workgroup minima / maxima into part
+ * (B * 2 * 128 floats of scratch), then a combine and the apply. */
+int cenet_augment_minmax(const float* x, float* y, float* part, int B, long n, cenet_stream_t stream);
+
 /* Test-time volume inference on the device (volresize.hip; src/utils/metrics_eval.py:37-84, utils_synapse.py:49-97).
  * cenet_vol_resize_cubic: scipy.ndimage.zoom(slice, (PH / H, PW / W), order=3) for n slices src [n, H, W] fp32 -> out
  * [n, 1, PH, PW] fp32, computed in fp64 in scipy's operation order (prefilter with mirror boundary along axis 0 then axis 1,
