@@ -362,6 +362,60 @@ def _postprocessed(pred_d: torch.Tensor, classes: int, postprocess, connectivity
     return keep_largest_component(pred_d, classes, connectivity, per_slice)[0]
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# flip / rotate test-time augmentation (csrc/tta.hip; the reference's tta_model of utils/utils.py:146-168 is the "flips" set, on
+# masks; here the class probabilities of the views are averaged).  Off unless asked for.
+# ---------------------------------------------------------------------------------------------------------------------
+TTA_SETS = kern.TTA_SETS
+
+
+def _tta_mask(tta, PH: int, PW: int) -> Tuple[int, int]:
+    """(view mask, T) of `tta` (a name of TTA_SETS or a tuple of view codes) for a [PH, PW] network input"""
+    mask, T = kern.tta_view_mask(tta)
+    if mask & 0xF0 and PH != PW:
+        raise ValueError(f"tta={tta!r} holds transposed views (codes 4..7), which need a square patch, got {(PH, PW)}")
+    return mask, T
+
+
+def _tta_device_only(tta, resize, on_dev):
+    """the volume wrappers run `tta` through predict_volume only: anything that would take the host route is an error"""
+    if tta is None:
+        return
+    kern.tta_view_mask(tta)
+    if resize != "device":
+        raise ValueError(f"tta={tta!r} needs resize='device', got resize={resize!r}")
+    if on_dev is None:
+        raise ValueError(f"tta={tta!r}: this case takes the host route (a 2-D input, or an axis of length 1 to resize), which has no "
+                         f"test-time augmentation")
+
+
+@torch.no_grad()
+def tta_predict(net, images: torch.Tensor, tta, labels: torch.Tensor = None):
+    """Test-time augmentation of a 2-D batch: images [B, C, H, W] -> (pred [B, H, W] class ids as float, conf [B, H, W]: the
+    winner's mean probability over the views, counts [K + 1, 3] int32 as `predict_counts` returns them, or None without `labels`).
+    The T views of `tta` are made in one launch, go through `net` as ONE batch [T * B, C, H, W], and one kernel un-views the T
+    logit stacks, averages their softmax and takes the argmax.  The network's mode and batch semantics are the caller's."""
+    if images.dim() != 4:
+        raise ValueError(f"images [B, C, H, W] expected, got {tuple(images.shape)}")
+    B, C, H, W = images.shape
+    mask, T = _tta_mask(tta, H, W)
+    if min(H, W) < 2:
+        raise ValueError(f"tta needs image sides >= 2, got {(H, W)}")
+    images = images.float().contiguous()
+    views = torch.empty((T * B, C, H, W), device=images.device, dtype=torch.float32)
+    kern.tta_views(images, views, B, C, H, W, mask)
+    logits = net(views).contiguous()
+    K = logits.shape[1]
+    pred = torch.empty((B, H, W), device=images.device, dtype=torch.float32)
+    conf = torch.empty_like(pred)
+    counts = None
+    if labels is not None:
+        labels = labels.reshape(B, H, W).float().contiguous()
+        counts = torch.empty((K + 1, 3), device=images.device, dtype=torch.int32)
+    kern.tta_argmax_resize_counts(logits, labels, pred, conf, counts, B, K, H, W, H, W, mask)
+    return pred, conf, counts
+
+
 def _device_case(image, label, device, patch_size):
     """image and label [D, H, W] on the device (one upload each), or None when the device resize does not take the case: a 2-D
     input, or an axis of length 1 that has to be resized (scipy special-cases those; the host path handles them)"""
@@ -409,18 +463,26 @@ def _save_case(test_save_path, case, z_spacing, prediction, image, label):
 
 @torch.no_grad()
 def predict_volume(net, volume: torch.Tensor, patch_size: Sequence[int], batch_slices: int = 32, normalize=None,
-                   labels: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                   labels: torch.Tensor = None, tta=None, conf_out: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The prediction loop of test_single_volume (metrics_eval.py:41-58, utils_synapse.py:53-76) without leaving the device:
     volume [D, H, W] on the device -> (prediction [D, H, W] class ids as float, counts [K + 1, 3] int64 over the whole volume
     when `labels` [D, H, W] is given, else None).  Per chunk of `batch_slices` slices: zoom(order=3) to `patch_size` (skipped when
     the slices already have it, as the reference does), optional `normalize = (mean, std)`, forward with the reference's batch-1
-    semantics, argmax + zoom(order=0) back in one kernel.  H, W and the patch sides must be >= 2 when they differ."""
+    semantics, argmax + zoom(order=0) back in one kernel.  H, W and the patch sides must be >= 2 when they differ.
+    `tta` (a name of TTA_SETS or a tuple of view codes; None: off): a chunk holds max(1, batch_slices // T) slices, whose T views go
+    through the network as one batch of at most `batch_slices`; one kernel un-views the logit stacks, averages their softmax, takes
+    the argmax and resizes back.  `conf_out` (with `tta` only): a [D, H, W] fp32 tensor on the volume's device that receives the
+    winning class's mean probability.  All sides must be >= 2 then."""
     assert volume.dim() == 3, "volume [D,H,W] expected"
     D, H, W = volume.shape
     PH, PW = int(patch_size[0]), int(patch_size[1])
     resize = (H != PH or W != PW)
     if resize and not kern.vol_resize_supported(H, W, PH, PW):
         raise ValueError(f"the device resize needs sides >= 2, got {(H, W)} -> {(PH, PW)}")
+    if tta is None and conf_out is not None:
+        raise ValueError("conf_out is the mean probability over the views of `tta`: it cannot be given with tta=None")
+    if tta is not None:
+        return _predict_volume_tta(net, volume, (PH, PW), batch_slices, normalize, labels, tta, conf_out)
     volume = volume.float().contiguous()
     pred = torch.empty((D, H, W), device=volume.device, dtype=torch.float32)
     total = None
@@ -449,11 +511,56 @@ def predict_volume(net, volume: torch.Tensor, patch_size: Sequence[int], batch_s
     return pred, total
 
 
+def _predict_volume_tta(net, volume, patch, batch_slices, normalize, labels, tta, conf_out):
+    """predict_volume with test-time augmentation: per chunk resize in (unchanged), views, one forward, fused merge"""
+    D, H, W = volume.shape
+    PH, PW = patch
+    mask, T = _tta_mask(tta, PH, PW)
+    if min(H, W, PH, PW) < 2:
+        raise ValueError(f"tta needs sides >= 2, got {(H, W)} -> {(PH, PW)}")
+    if conf_out is not None and (tuple(conf_out.shape) != (D, H, W) or conf_out.dtype != torch.float32
+                                 or conf_out.device != volume.device or not conf_out.is_contiguous()):
+        raise ValueError(f"conf_out: a contiguous fp32 tensor {(D, H, W)} on {volume.device} expected, got "
+                         f"{tuple(conf_out.shape)} {conf_out.dtype} on {conf_out.device}")
+    resize = (H != PH or W != PW)
+    chunk = max(1, batch_slices // T)
+    volume = volume.float().contiguous()
+    pred = torch.empty((D, H, W), device=volume.device, dtype=torch.float32)
+    total = None
+    if labels is not None:
+        labels = labels.reshape(D, H, W).float().contiguous()
+    stage = torch.empty(min(D, chunk) * H * W, device=volume.device, dtype=torch.float64) if resize else None
+    for s in range(0, D, chunk):
+        sl = volume[s:s + chunk]
+        n = sl.shape[0]
+        if resize:
+            inp = torch.empty((n, 1, PH, PW), device=volume.device, dtype=torch.float32)
+            kern.vol_resize_cubic(sl, stage, inp, n, H, W, PH, PW, normalize)
+        else:
+            inp = sl.unsqueeze(1)
+            if normalize is not None:
+                inp = (inp - normalize[0]) / normalize[1]
+            inp = inp.contiguous()
+        views = torch.empty((T * n, 1, PH, PW), device=volume.device, dtype=torch.float32)
+        kern.tta_views(inp, views, n, 1, PH, PW, mask)
+        with ops.batch1_semantics():  # every view of every slice is computed as a batch-1 forward would compute it
+            logits = net(views).contiguous()
+        K = logits.shape[1]
+        counts = None
+        if labels is not None:
+            counts = torch.empty((K + 1, 3), device=volume.device, dtype=torch.int32)
+        kern.tta_argmax_resize_counts(logits, None if labels is None else labels[s:s + n], pred[s:s + n],
+                                      None if conf_out is None else conf_out[s:s + n], counts, n, K, PH, PW, H, W, mask)
+        if counts is not None:
+            total = counts.long() if total is None else total + counts.long()
+    return pred, total
+
+
 @torch.no_grad()
 def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int] = (224, 224), batch_slices: int = 32,
                        device=None, resize: str = "host", test_save_path=None, case=None,
                        z_spacing: float = 1.0, postprocess=None, lcc_connectivity: int = 1,
-                       lcc_per_slice: bool = False) -> List[Tuple[float, float, float, float]]:
+                       lcc_per_slice: bool = False, tta=None) -> List[Tuple[float, float, float, float]]:
     """test_single_volume (metrics_eval.py:37-84) for a 3-D volume: image / label [1,D,H,W] or [D,H,W] (tensor or ndarray).
     Slices are resized to `patch_size` with scipy's cubic zoom and the predictions back with order 0 exactly as the
     reference does (host side), but the network runs on batches of slices and the metrics on the device.
@@ -461,6 +568,8 @@ def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int
     device resize does not take (an axis of length 1) goes the host way.  `test_save_path`: see `_save_case`.
     `postprocess="lcc"`: the prediction goes through `keep_largest_component(pred, classes, lcc_connectivity, lcc_per_slice)` on
     the device before it is scored and saved (not in the reference; None: no such step).
+    `tta` (a name of TTA_SETS or a tuple of view codes): test-time augmentation inside `predict_volume`, before `postprocess`;
+    it needs resize="device" and a case the device resize takes, and raises ValueError otherwise.
     Returns [(dice, hd95, jaccard, assd)] for classes 1..classes-1."""
     from scipy.ndimage import zoom
     assert resize in ("host", "device"), resize
@@ -468,8 +577,9 @@ def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int
     device = device or next(net.parameters()).device
     net.eval()
     on_dev = _device_case(image, label, device, patch_size) if resize == "device" else None
+    _tta_device_only(tta, resize, on_dev)
     if on_dev is not None:
-        pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices)
+        pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices, tta=tta)
         pred_d = _postprocessed(pred_d, classes, postprocess, lcc_connectivity, lcc_per_slice)
         if test_save_path is not None:
             _save_case(test_save_path, case, z_spacing, pred_d, on_dev[0], on_dev[1])
@@ -523,7 +633,7 @@ def synapse_metric_percase(pred: torch.Tensor, gt: torch.Tensor, method: str = "
 @torch.no_grad()
 def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequence[int] = (256, 256), test_save_path=None,
                                case=None, z_spacing: float = 1.0, batch_slices: int = 32, device=None, resize: str = "host",
-                               postprocess=None, lcc_connectivity: int = 1, lcc_per_slice: bool = False):
+                               postprocess=None, lcc_connectivity: int = 1, lcc_per_slice: bool = False, tta=None):
     """test_single_volume of utils_synapse.py:49-97: every slice of the volume [1, D, H, W] is resized to `patch_size` (cubic
     zoom), normalised with Normalize([0.5], [0.5]) (`ToTensor` leaves float arrays unscaled), classified, and the prediction
     resized back with order 0; returns [(dice, hd95)] for classes 1..classes-1.  A 2-D input takes the reference's second branch
@@ -531,15 +641,16 @@ def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequ
     the metrics run on the device.  `test_save_path` (NIfTI files through SimpleITK, which is absent here) writes .npy volumes
     with the spacing (1, 1, z_spacing) in a side-car text file instead.  `resize="device"`: as for `test_single_volume`, with the
     normalisation inside the resize kernel; the 2-D branch has no resize and is the same in both modes.  `postprocess`,
-    `lcc_connectivity`, `lcc_per_slice`: as for `test_single_volume`."""
+    `lcc_connectivity`, `lcc_per_slice`, `tta`: as for `test_single_volume` (the 2-D branch takes no `tta`: ValueError)."""
     from scipy.ndimage import zoom
     assert resize in ("host", "device"), resize
     _check_postprocess(postprocess)
     device = device or next(net.parameters()).device
     net.eval()
     on_dev = _device_case(image, label, device, patch_size) if resize == "device" else None
+    _tta_device_only(tta, resize, on_dev)
     if on_dev is not None:
-        pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices, normalize=(0.5, 0.5))
+        pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices, normalize=(0.5, 0.5), tta=tta)
         pred_d = _postprocessed(pred_d, classes, postprocess, lcc_connectivity, lcc_per_slice)
         if test_save_path is not None:
             _save_case(test_save_path, case, z_spacing, pred_d, on_dev[0], on_dev[1])
@@ -578,17 +689,19 @@ def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequ
 
 @torch.no_grad()
 def val_single_volume(image, label, net, classes: int, patch_size: Sequence[int] = (224, 224), batch_slices: int = 32,
-                      device=None, resize: str = "device") -> List[float]:
+                      device=None, resize: str = "device", tta=None) -> List[float]:
     """val_single_volume (metrics_eval.py:87-122): the prediction of `test_single_volume`, scored with calculate_dice_percase
     only — Dice of classes 1..classes-1 over the whole volume.  `resize="device"`: the overlap counts come out of the argmax +
     resize-back kernel, nothing but those 3 (K + 1) integers leaves the device.  `resize="host"` (and cases the device resize
-    does not take): the reference's host resizes, counts from the device."""
+    does not take): the reference's host resizes, counts from the device.  `tta`: as for `test_single_volume`; the counts then
+    come out of the merge kernel."""
     assert resize in ("host", "device"), resize
     device = device or next(net.parameters()).device
     net.eval()
     on_dev = _device_case(image, label, device, patch_size) if resize == "device" else None
+    _tta_device_only(tta, resize, on_dev)
     if on_dev is not None:
-        _, counts = predict_volume(net, on_dev[0], patch_size, batch_slices, labels=on_dev[1])
+        _, counts = predict_volume(net, on_dev[0], patch_size, batch_slices, labels=on_dev[1], tta=tta)
         return class_dice(counts)[:classes - 1]
     image = image.squeeze(0).cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
     label = label.squeeze(0).cpu().numpy() if torch.is_tensor(label) else np.asarray(label)
@@ -607,14 +720,16 @@ def val_single_volume(image, label, net, classes: int, patch_size: Sequence[int]
 @torch.no_grad()
 def inference(net, volumes, classes: int, patch_size: Sequence[int] = (224, 224), z_spacing: float = 1.0, test_save_path=None,
               log=print, resize: str = "device", batch_slices: int = 32, device=None, postprocess=None,
-              lcc_connectivity: int = 1, lcc_per_slice: bool = False) -> Tuple[float, float]:
+              lcc_connectivity: int = 1, lcc_per_slice: bool = False, tta=None) -> Tuple[float, float]:
     """inference (utils_acdc.py:7-33): `test_single_volume` for every case of `volumes` (the test loader's dicts: `image`
     [1, D, H, W], `label`, `case_name` — a string or the DataLoader's one-element list), the reference's per-case and per-class
     log lines through `log`, and (mean dice, mean hd95): the metric table averaged over the cases, then over the classes.
-    `postprocess`, `lcc_connectivity`, `lcc_per_slice` go to `test_single_volume`."""
+    `postprocess`, `lcc_connectivity`, `lcc_per_slice` and `tta` go to `test_single_volume`."""
     _check_postprocess(postprocess)
     post = {} if postprocess is None else dict(postprocess=postprocess, lcc_connectivity=lcc_connectivity,
                                                lcc_per_slice=lcc_per_slice)
+    if tta is not None:
+        post["tta"] = tta
     net.eval()
     total, n = 0.0, 0
     for i, batch in enumerate(volumes):
@@ -647,30 +762,31 @@ def _binary_dc(result: torch.Tensor, reference: torch.Tensor) -> float:
 
 
 @torch.no_grad()
-def skin_val(net, vl_loader, device=None) -> float:
-    """val of utils_skin.py:97-113: mean over the loader's batches of dc(argmax(softmax(logits), 1).squeeze(0), label batch)"""
+def skin_val(net, vl_loader, device=None, tta=None) -> float:
+    """val of utils_skin.py:97-113: mean over the loader's batches of dc(argmax(softmax(logits), 1).squeeze(0), label batch).
+    `tta`: the prediction of `tta_predict` instead of the plain argmax."""
     device = device or next(net.parameters()).device
     net.eval()
     dc_sum, n = 0.0, 0
     for batch in vl_loader:
         img, lab = batch["image"].to(device), batch["label"].to(device)
-        pred, _ = predict_counts(net(img.float()))
+        pred = predict_counts(net(img.float()))[0] if tta is None else tta_predict(net, img.float(), tta)[0]
         dc_sum += _binary_dc(pred.squeeze(0), lab)
         n += 1
     return dc_sum / max(n, 1)
 
 
 @torch.no_grad()
-def skin_test(net, te_loader, device=None) -> Tuple[float, float, float]:
+def skin_test(net, te_loader, device=None, tta=None) -> Tuple[float, float, float]:
     """test of utils_skin.py:131-170 (batch size 1, as the reference's test loader): (mean dice, pixel accuracy, mean IoU) with
     the ground truth read as `label[0, 0]` and calc_iou(pd > 0.5, gt > 0.5) = |A & B| / |A or B| (0.0 for an empty union,
-    utils_skin.py:13-27)"""
+    utils_skin.py:13-27).  `tta`: the prediction of `tta_predict` instead of the plain argmax."""
     device = device or next(net.parameters()).device
     net.eval()
     dc_sum, correct, total, ious, n = 0.0, 0, 0, [], 0
     for batch in te_loader:
         img, lab = batch["image"].float().to(device), batch["label"].float().to(device)
-        pred, _ = predict_counts(net(img))
+        pred = predict_counts(net(img))[0] if tta is None else tta_predict(net, img, tta)[0]
         pd = pred.squeeze(0)
         gt = lab[0, 0]
         correct += int((pd == gt).sum())

@@ -1398,6 +1398,53 @@ def argmax_resize_counts(logits, labels, pred, counts, n, K, PH, PW, H, W):
     _call("cenet_argmax_resize_counts_f32", logits, labels, pred, counts, n, K, PH, PW, H, W)
 
 
+# test-time augmentation (tta.hip): a view is an element of D4 coded 0..7 (bit 0 flip along W, bit 1 flip along H, bit 2 transpose), a
+# view set a mask of those codes
+TTA_SETS = {"flips": 0b0000_0111, "flips4": 0b0000_1111, "d4": 0xFF}
+
+
+def tta_view_mask(tta):
+    """(view mask, number of views T) of a named set of TTA_SETS or a tuple of view codes 0..7"""
+    if isinstance(tta, str):
+        if tta not in TTA_SETS:
+            raise ValueError(f"tta: one of {sorted(TTA_SETS)} or a tuple of view codes 0..7 expected, got {tta!r}")
+        mask = TTA_SETS[tta]
+    else:
+        codes = list(tta) if isinstance(tta, (tuple, list)) else None
+        if not codes or any(not isinstance(g, int) or isinstance(g, bool) or not 0 <= g <= 7 for g in codes):
+            raise ValueError(f"tta: one of {sorted(TTA_SETS)} or a non-empty tuple of view codes 0..7 expected, got {tta!r}")
+        mask = 0
+        for g in codes:
+            mask |= 1 << g
+    return mask, bin(mask).count("1")
+
+
+def _tta_views_of(view_mask):
+    """T of a valid mask; 1 for one the entry point refuses (so that the refusal is the library's, with its name)"""
+    return bin(view_mask).count("1") if 1 <= view_mask <= 255 else 1
+
+
+def tta_views(src, out, n, C, PH, PW, view_mask):
+    """cenet_tta_views_f32 (tta.hip): src [n, C, PH, PW] fp32 -> out [T, n, C, PH, PW], the views of `view_mask` in ascending code
+    order, one launch"""
+    assert src.is_contiguous() and out.is_contiguous()
+    assert src.numel() == n * C * PH * PW and out.numel() == _tta_views_of(view_mask) * n * C * PH * PW
+    _launch("cenet_tta_views_f32", src, out, n, C, PH, PW, view_mask)
+
+
+def tta_argmax_resize_counts(logits, labels, pred, conf, counts, n, K, PH, PW, H, W, view_mask):
+    """cenet_tta_argmax_resize_counts (tta.hip): logits [T, n, K, PH, PW] fp32 / bf16, one stack per view -> pred [n, H, W] class ids
+    as float (un-view + softmax + mean over the views + argmax + zoom(order=0) in one pass) and conf [n, H, W] (or None), the
+    winner's mean probability; labels / counts as for argmax_resize_counts"""
+    assert logits.is_contiguous() and pred.is_contiguous()
+    assert logits.numel() == _tta_views_of(view_mask) * n * K * PH * PW and pred.numel() == n * H * W
+    assert conf is None or (conf.is_contiguous() and conf.numel() == n * H * W)
+    if labels is not None:
+        assert labels.is_contiguous() and labels.numel() == n * H * W
+        assert counts is None or counts.numel() == (K + 1) * 3
+    _call("cenet_tta_argmax_resize_counts_f32", logits, labels, pred, conf, counts, n, K, PH, PW, H, W, view_mask)
+
+
 def layernorm_fwd_acc(acc, bias, xpre, gamma, beta, y, mean, rstd, rows, Cn, eps):
     """cenet_layernorm_fwd_acc_bf16: LayerNorm straight from a split-K fp32 accumulator (+ bias); acc is zero afterwards"""
     _launch("cenet_layernorm_fwd_acc_bf16", acc, bias, xpre, gamma, beta, y, mean, rstd, rows, Cn, eps)

@@ -1132,6 +1132,26 @@ int cenet_argmax_resize_counts_f32(const float* logits, const float* labels, flo
 int cenet_argmax_resize_counts_bf16(const unsigned short* logits, const float* labels, float* pred, unsigned* counts, int n, int K,
                                     int PH, int PW, int H, int W, cenet_stream_t stream);
 
+/* Flip / rotate test-time augmentation (tta.hip).  A view is an element g of the dihedral group D4 as a bit field: bit 0 flip
+ * along W, bit 1 flip along H, bit 2 transpose H and W; forward v = x; g & 4: v = v^T; g & 2: v = flip_H(v); g & 1: v = flip_W(v).
+ * view_mask: bit g set = view g is used, 1..255; the T = popcount(view_mask) views are taken in ascending code order.  Views with
+ * bit 2 need PH == PW.
+ * cenet_tta_views_f32: src [n, C, PH, PW] -> out [T, n, C, PH, PW], every view in one launch (bit copies).
+ * cenet_tta_argmax_resize_counts_*: logits [T, n, K, PH, PW], stack t computed from view t of the input -> pred [n, H, W] (class
+ * ids as floats): at the source pixel that zoom(order=0) picks (the rule of cenet_argmax_resize_counts_*, class 0 where the
+ * coordinate exceeds PH - 1 or PW - 1) every view's K logits are read at that pixel's place in the view, turned into a
+ * max-subtracted fp32 softmax and summed in view order; pred is the first maximum of the sums under `>`.  conf (or NULL):
+ * [n, H, W], sum[pred] * (1.0f / T), 0 where the coordinate is outside.  labels / counts as for cenet_argmax_resize_counts_*.
+ * Non-finite logits are not special-cased: a NaN sum never wins under `>`.  CENET_EINVAL for a null logits / pred, labels
+ * without counts, a view_mask outside 1..255, a transposed view with PH != PW, K outside 1..16, a side < 2 (cenet_tta_views_f32:
+ * < 1) or a plane of more than 2^31 - 1 pixels. */
+int cenet_tta_views_f32(const float* src, float* out, int n, int C, int PH, int PW, int view_mask, cenet_stream_t stream);
+int cenet_tta_argmax_resize_counts_f32(const float* logits, const float* labels, float* pred, float* conf, unsigned* counts, int n,
+                                       int K, int PH, int PW, int H, int W, int view_mask, cenet_stream_t stream);
+int cenet_tta_argmax_resize_counts_bf16(const unsigned short* logits, const float* labels, float* pred, float* conf,
+                                        unsigned* counts, int n, int K, int PH, int PW, int H, int W, int view_mask,
+                                        cenet_stream_t stream);
+
 /* LayerNorm of a split-K accumulator (norm.hip, round 5; pvtv2.py:93-95,99-100: sr conv -> norm): acc [rows, C] fp32 holds the
  * conv's products (zero-at-rest accumulator of a split-K GEMM); xpre = bf16(acc + bias) (the rows the LayerNorm backward reads),
  * y = LayerNorm(xpre) * gamma + beta, mean / rstd [rows]; acc is left zero.  bias may be NULL.  C % 4 == 0, C <= 512. */

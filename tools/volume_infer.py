@@ -13,7 +13,9 @@ above --metrics-cap pairs the metrics are stubbed out (in BOTH modes) and the li
 five, spread, all methods in this one process): per volume size the network's prediction and a uniform-noise prediction against the
 blob labels, under the parent's per-class `metric_percase(method="pairs")` loop, `pairs`, `edt` and `auto`; and the crossover scan
 behind `evaluate.AUTO_PAIRS_PER_BOX_VOXEL`: two overlapping balls of growing radius under both methods.  Prints one JSON line.
-    python tools/volume_infer.py [--bf16] [--only acdc|synapse] [--metrics pairs|edt|auto] [--metrics-cap 5e10] [--report]"""
+--tta NAME adds a third mode, `device_tta`: resize="device" with that view set of evaluate.TTA_SETS (its split has `tta_views`, and
+`resize_back` is the fused merge).
+    python tools/volume_infer.py [--bf16] [--only acdc|synapse] [--metrics pairs|edt|auto] [--metrics-cap 5e10] [--report] [--tta NAME]"""
 import argparse
 import json
 import os
@@ -64,27 +66,31 @@ class Parts:
         return timed
 
 
-def call(net, image, label, mode, dev):
+def call(net, image, label, mode, dev, tta=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    m = evaluate.test_single_volume(image, label, net, K, patch_size=PATCH, batch_slices=32, device=dev, resize=mode)
+    m = evaluate.test_single_volume(image, label, net, K, patch_size=PATCH, batch_slices=32, device=dev, resize=mode, tta=tta)
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3, m
 
 
-def split_call(net, image, label, mode, dev):
+def split_call(net, image, label, mode, dev, tta=None):
     """one call with every part wrapped; the wrappers are taken off again"""
     p = Parts()
-    saved = (scipy.ndimage.zoom, kern.vol_resize_cubic, kern.argmax_resize_counts, evaluate.label_metrics, net.forward)
+    saved = (scipy.ndimage.zoom, kern.vol_resize_cubic, kern.argmax_resize_counts, evaluate.label_metrics, net.forward,
+             kern.tta_views, kern.tta_argmax_resize_counts)
+    kern.tta_views = p.wrap("tta_views", saved[5])
+    kern.tta_argmax_resize_counts = p.wrap("resize_back", saved[6])
     scipy.ndimage.zoom = p.wrap(lambda *a, **k: "resize_in" if k.get("order", 3) == 3 else "resize_back", saved[0])
     kern.vol_resize_cubic = p.wrap("resize_in", saved[1])
     kern.argmax_resize_counts = p.wrap("resize_back", saved[2])
     evaluate.label_metrics = p.wrap("metrics", saved[3])
     net.forward = p.wrap("forward", saved[4])
     try:
-        total, _ = call(net, image, label, mode, dev)
+        total, _ = call(net, image, label, mode, dev, tta)
     finally:
         scipy.ndimage.zoom, kern.vol_resize_cubic, kern.argmax_resize_counts, evaluate.label_metrics = saved[:4]
+        kern.tta_views, kern.tta_argmax_resize_counts = saved[5:]
         del net.forward
     p.t["other"] = total - sum(p.t.values())
     p.t["total"] = total
@@ -170,6 +176,8 @@ def main():
     ap.add_argument("--metrics-cap", type=float, default=5e10)
     ap.add_argument("--metrics", choices=evaluate.METHODS, default="auto")
     ap.add_argument("--report", action="store_true")
+    ap.add_argument("--tta", choices=sorted(evaluate.TTA_SETS), default=None,
+                    help="also time resize='device' with this test-time augmentation set (entry `device_tta`)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     kw = MODEL_CONFIGS["acdc"]["kw"]
@@ -178,7 +186,7 @@ def main():
     net = net.to(dev).eval()
     kern.set_compute_bf16(args.bf16)
     res = {"tool": "volume_infer", "device": torch.cuda.get_device_name(0), "kernel_src_sha16": build.source_sha16(),
-           "precision": "bf16" if args.bf16 else "fp32", "patch": list(PATCH), "batch_slices": 32, "unit": "ms", "metrics_method": args.metrics, "volumes": {}}
+           "precision": "bf16" if args.bf16 else "fp32", "patch": list(PATCH), "batch_slices": 32, "unit": "ms", "metrics_method": args.metrics, "tta": args.tta, "volumes": {}}
     real_metric = evaluate.label_metrics
     for name, shape in VOLUMES.items():
         if args.only and name != args.only:
@@ -195,15 +203,16 @@ def main():
             evaluate.label_metrics = lambda p, g, k, kind="acdc", method=None: [(0.0, 0.0, 0.0, 0.0)] * (k - 1)
         entry = {"shape": list(shape), "max_border_pairs": pairs, "metrics_timed": timed_metrics}
         preds = {}
-        for mode in ("host", "device"):
-            call(net, image, label, mode, dev)  # warm-up
-            runs = [call(net, image, label, mode, dev)[0] for _ in range(5)]
-            splits = [split_call(net, image, label, mode, dev) for _ in range(3)]
+        for mode, tta in [("host", None), ("device", None)] + ([("device_tta", args.tta)] if args.tta else []):
+            how = mode.split("_")[0]
+            call(net, image, label, how, dev, tta)  # warm-up
+            runs = [call(net, image, label, how, dev, tta)[0] for _ in range(5)]
+            splits = [split_call(net, image, label, how, dev, tta) for _ in range(3)]
             keys = sorted(set().union(*splits))
             entry[mode] = {"total_runs": [round(v, 3) for v in runs], "total_median": round(statistics.median(runs), 3),
                            "total_spread": round(max(runs) - min(runs), 3),
                            "split_median": {k: round(statistics.median(s.get(k, 0.0) for s in splits), 3) for k in keys}}
-            preds[mode] = evaluate.val_single_volume(image, label, net, K, patch_size=PATCH, device=dev, resize=mode)
+            preds[mode] = evaluate.val_single_volume(image, label, net, K, patch_size=PATCH, device=dev, resize=how, tta=tta)
         evaluate.label_metrics = real_metric
         entry["speedup"] = round(entry["host"]["total_median"] / entry["device"]["total_median"], 3)
         entry["class_dice"] = {m: [round(v, 6) for v in preds[m]] for m in preds}
