@@ -1,15 +1,17 @@
 // edt.hip — surface metrics by an exact distance transform (evaluate.label_metrics, surface_distances(method="edt")).
 // medpy's __surface_distances reads the Euclidean distance transform of the complement of one border at the voxels of the other
 // border; metrics.hip restates that as an all-pairs minimum, which is quadratic in the border sizes.  Here the transform itself
-// runs on the device: linear in the number of voxels, whatever the masks look like.  Unit spacing, so every squared distance is
-// an integer and everything below is integer arithmetic (no atomics in the transform, bit-reproducible).
+// runs on the device: linear in the number of voxels, whatever the masks look like.  With unit spacing every squared distance is
+// an integer and the transform is integer arithmetic; with a voxel spacing (cenet_edt_sq_spaced_u8) the line passes that carry a
+// weight run in fp64.  No atomics in either transform: bit-reproducible.
 //   label_borders_kernel   one pass over two label volumes: per class the border flags of both, the overlap counts, the border
 //                          counts and the borders' bounding boxes
 //   edt_x_kernel           squared distance to the nearest feature voxel within each row, rows staged through LDS
 //   edt_line_kernel        g[j] + (u - j)^2 minimised over j along y or z: lower envelope of parabolas with the integer Sep of
 //                          Meijster, Roerdink & Hesselink (2000), one thread per line, consecutive lanes = consecutive x
+//   edt_line_w_kernel      the same line pass with a voxel spacing, in fp64: g[j] + w2 (u - j)^2 (cenet_edt_sq_spaced_u8)
 //   border_count / border_gather   order-preserving compaction of a border: coordinates (for the all-pairs kernel) or the
-//                          transform's values in C order of the border voxels
+//                          transform's values (int32, or fp64 for the spaced transform) in C order of the border voxels
 //   dm_labels / dm_logits / dm_merge   boundary-distance maps of a stack of 2-D class planes for the distance-map losses
 //                          (dist_loss.hip): the planes' masks and their complements as one stack of features, the x and y passes
 //                          above over that stack, and the sum of the two halves
@@ -199,10 +201,104 @@ __global__ __launch_bounds__(64) void edt_line_kernel(const int* __restrict__ g,
   }
 }
 
+// ---- y / z pass with a voxel spacing ------------------------------------------------------------------------------------------
+// out[u] = min over j with g[j] finite of g[j] + w2 (u - j)^2 in fp64, w2 = the squared spacing along the line: the kernel above
+// with the same lines, the same access pattern and the same two scans.  G = int: g is the x pass's integer dx^2, scaled by
+// `gscale` (the squared x spacing) on load, EDT_INF read as +inf (the y pass); G = double: g as it is (the z pass).  A site without
+// a finite g is skipped, so no infinity enters the arithmetic; a line without a site comes out +inf.
+// The stack lives in the line's own 8-byte slots of `out`, as in the integer kernel: s in the low and t in the high 32 bits of the
+// slot (a bit pattern with a zero exponent, only ever copied), no separate workspace.  "Entry q sits at slot q <= t[q] <= u" holds
+// whatever the rounding does, because t is forced to grow strictly from one entry to the next: Sep is floor(num / den) in fp64,
+// which rounding can put one below the t of the entry under it, and the new entry then starts at t + 1.  Such a tie is between two
+// sites whose values at that position agree to rounding.  Products and sums are exact for dyadic spacings at these sizes.
+#ifdef __clang__
+#pragma clang fp contract(off)  // w2 * d^2 + g as a product and a sum, on the device as on the host checker
+#endif
+#define EDT_DINF __builtin_huge_val()
+template <typename G>
+__device__ __forceinline__ double edtw_ld(const G* __restrict__ g, long k, double gscale);
+template <>
+__device__ __forceinline__ double edtw_ld<int>(const int* __restrict__ g, long k, double gscale) {
+  const int v = g[k];
+  return v == EDT_INF ? EDT_DINF : gscale * (double)v;
+}
+template <>
+__device__ __forceinline__ double edtw_ld<double>(const double* __restrict__ g, long k, double) {
+  return g[k];
+}
+__device__ __forceinline__ double edtw_f(int u, int s, double gs, double w2) {
+  const double d = (double)(u - s);
+  return w2 * (d * d) + gs;
+}
+__device__ __forceinline__ void edtw_put(double* slot, int s, int t) {
+  const unsigned long long e = (unsigned long long)(unsigned)s | ((unsigned long long)(unsigned)t << 32);
+  double d;
+  __builtin_memcpy(&d, &e, 8);
+  *slot = d;
+}
+__device__ __forceinline__ void edtw_get(const double* slot, int& s, int& t) {
+  const double d = *slot;
+  unsigned long long e;
+  __builtin_memcpy(&e, &d, 8);
+  s = (int)(unsigned)(e & 0xffffffffull), t = (int)(unsigned)(e >> 32);
+}
+template <typename G>
+__global__ __launch_bounds__(64) void edt_line_w_kernel(const G* __restrict__ g, double* __restrict__ out, long inner,
+                                                       long outer_stride, int m, long es, double w2, double gscale) {
+  const long i = (long)blockIdx.x * 64 + threadIdx.x;
+  if (i >= inner) return;
+  const long base = (long)blockIdx.y * outer_stride + i;
+  g += base;
+  out += base;
+  int q = -1, s = 0, t = 0;  // top of the stack, kept in registers
+  double gs = 0.0;
+  for (int u = 0; u < m; ++u) {
+    const double gu = edtw_ld<G>(g, u * es, gscale);
+    if (gu == EDT_DINF) continue;
+    while (q >= 0 && edtw_f(t, s, gs, w2) > edtw_f(t, u, gu, w2)) {
+      if (--q >= 0) {
+        edtw_get(out + q * es, s, t);
+        gs = edtw_ld<G>(g, s * es, gscale);
+      }
+    }
+    if (q < 0) {
+      q = 0, s = u, t = 0, gs = gu;
+      edtw_put(out, u, 0);
+    } else {
+      // Sep(s, u) = floor((w2 (u^2 - s^2) + g(u) - g(s)) / (2 w2 (u - s)))
+      const double num = w2 * (double)((long long)u * u - (long long)s * s) + (gu - gs);
+      const double sep = floor(num / (2.0 * w2 * (double)(u - s)));
+      if (sep < (double)(m - 1)) {  // (so the conversion below is in range)
+        const int w = sep < (double)t ? t + 1 : 1 + (int)sep;
+        if (w < m) {
+          ++q, s = u, t = w, gs = gu;
+          edtw_put(out + q * es, s, t);
+        }
+      }
+    }
+  }
+  if (q < 0) {
+    for (int u = 0; u < m; ++u) out[u * es] = EDT_DINF;
+    return;
+  }
+  for (int u = m - 1; u >= 0; --u) {
+    const bool pop = (u == t);
+    int ns = s, nt = t;
+    double ngs = gs;
+    if (pop && q > 0) {
+      edtw_get(out + (q - 1) * es, ns, nt);
+      ngs = edtw_ld<G>(g, ns * es, gscale);
+    }
+    out[u * es] = edtw_f(u, s, gs, w2);
+    if (pop) --q, s = ns, t = nt, gs = ngs;
+  }
+}
+
 // ---- ordered compaction of a border ------------------------------------------------------------------------------------------
 // A workgroup owns CP_CHUNK consecutive voxels.  border_count: how many of them carry `match`.  border_gather: with the exclusive
 // prefix sum of those counts (taken between the two launches), writes for every matching voxel, in C order, either its (z, y, x)
-// or src[voxel].  Thread t ranks the 16 voxels [16 t, 16 t + 16) of the chunk after a block scan of the per-thread counts.
+// or src[voxel] (T = int; T = double: src[voxel] only).  Thread t ranks the 16 voxels [16 t, 16 t + 16) of the chunk after a block
+// scan of the per-thread counts.
 #define CP_CHUNK 4096
 __global__ __launch_bounds__(256) void border_count_kernel(const unsigned char* __restrict__ bl, int match, long n,
                                                           int* __restrict__ counts) {
@@ -217,9 +313,10 @@ __global__ __launch_bounds__(256) void border_count_kernel(const unsigned char* 
   __syncthreads();
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
+template <typename T>
 __global__ __launch_bounds__(256) void border_gather_kernel(const unsigned char* __restrict__ bl, int match, long n, int H, int W,
-                                                           const int* __restrict__ offs, const int* __restrict__ src,
-                                                           int* __restrict__ out) {
+                                                           const int* __restrict__ offs, const T* __restrict__ src,
+                                                           T* __restrict__ out) {
   __shared__ unsigned char fl[CP_CHUNK];
   __shared__ int cnt[256];
   const int tid = threadIdx.x;
@@ -245,7 +342,7 @@ __global__ __launch_bounds__(256) void border_gather_kernel(const unsigned char*
       out[pos] = src[i];
     } else {
       const long t = i / W;
-      out[pos * 3] = (int)(t / H), out[pos * 3 + 1] = (int)(t % H), out[pos * 3 + 2] = (int)(i % W);
+      out[pos * 3] = (T)(t / H), out[pos * 3 + 1] = (T)(t % H), out[pos * 3 + 2] = (T)(i % W);
     }
     ++pos;
   }
@@ -284,6 +381,42 @@ extern "C" int cenet_edt_sq_u8(const unsigned char* feat, int match, int* tmp, i
   const int rc = edt_planes_launch(feat, match, d2, tmp, D, H, W, stream);
   if (rc != CENET_OK) return rc;
   CENET_LAUNCH(edt_line_kernel, dim3(edt_cdiv(plane, 64), 1u), dim3(64), stream, (const int*)tmp, d2, plane, 0L, D, plane);
+  CENET_CHECK_LAUNCH();
+  return CENET_OK;
+}
+
+// The transform with a voxel spacing: the integer x pass, then the weighted line pass along y (which scales the x result by sx^2 as
+// it loads it) and along z; with sy == sx the integer y pass as well, and one weighted pass.  xd: D*H*W ints, tmp and d2: D*H*W
+// doubles each.
+static inline bool edt_spacing_ok(double s) {
+  const double w2 = s * s;
+  return s > 0.0 && w2 > 0.0 && w2 - w2 == 0.0;  // positive and finite, and so is its square
+}
+extern "C" int cenet_edt_sq_spaced_u8(const unsigned char* feat, int match, int* xd, double* tmp, double* d2, int D, int H, int W,
+                                      double sz, double sy, double sx, hipStream_t stream) {
+  if (D <= 0 || H <= 0 || W <= 0 || match > 255) return CENET_EINVAL;
+  if (!edt_spacing_ok(sz) || !edt_spacing_ok(sy) || !edt_spacing_ok(sx)) return CENET_EINVAL;
+  if ((long)D * D + (long)H * H + (long)W * W >= (1L << 31)) return CENET_EINVAL;  // the x pass is int32, the stack packs sides
+  const long rows = (long)D * H, plane = (long)H * W;
+  if (plane * D >= (1L << 40) || edt_cdiv(rows, EX_ROWS) == 0) return CENET_EINVAL;
+  if (sy == sx) {
+    // the in-plane spacing is isotropic (every clinical volume): the integer passes give dy^2 + dx^2 exactly, into the first half of
+    // tmp, and only the z pass is weighted: sz^2 dz^2 + sx^2 (dy^2 + dx^2), the in-plane scale applied as the z pass loads
+    int* yd = (int*)tmp;
+    const int rc = edt_planes_launch(feat, match, xd, yd, D, H, W, stream);
+    if (rc != CENET_OK) return rc;
+    CENET_LAUNCH(edt_line_w_kernel<int>, dim3(edt_cdiv(plane, 64), 1u), dim3(64), stream, (const int*)yd, d2, plane, 0L, D, plane,
+                 sz * sz, sx * sx);
+    CENET_CHECK_LAUNCH();
+    return CENET_OK;
+  }
+  CENET_LAUNCH(edt_x_kernel, dim3(edt_cdiv(rows, EX_ROWS)), dim3(256), stream, feat, match, xd, rows, W);
+  CENET_CHECK_LAUNCH();
+  CENET_LAUNCH(edt_line_w_kernel<int>, dim3(edt_cdiv(W, 64), (unsigned)D), dim3(64), stream, (const int*)xd, tmp, (long)W, plane, H,
+               (long)W, sy * sy, sx * sx);
+  CENET_CHECK_LAUNCH();
+  CENET_LAUNCH(edt_line_w_kernel<double>, dim3(edt_cdiv(plane, 64), 1u), dim3(64), stream, (const double*)tmp, d2, plane, 0L, D,
+               plane, sz * sz, 1.0);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
 }
@@ -412,7 +545,16 @@ extern "C" int cenet_border_gather_i32(const unsigned char* bl, int match, int D
                                        int* out, hipStream_t stream) {
   if (D <= 0 || H <= 0 || W <= 0 || match < 0 || match > 255) return CENET_EINVAL;
   const long n = (long)D * H * W;
-  CENET_LAUNCH(border_gather_kernel, dim3(edt_cdiv(n, CP_CHUNK)), dim3(256), stream, bl, match, n, H, W, offs, src, out);
+  CENET_LAUNCH(border_gather_kernel<int>, dim3(edt_cdiv(n, CP_CHUNK)), dim3(256), stream, bl, match, n, H, W, offs, src, out);
+  CENET_CHECK_LAUNCH();
+  return CENET_OK;
+}
+
+extern "C" int cenet_border_gather_f64(const unsigned char* bl, int match, int D, int H, int W, const int* offs, const double* src,
+                                       double* out, hipStream_t stream) {
+  if (D <= 0 || H <= 0 || W <= 0 || match < 0 || match > 255 || !src) return CENET_EINVAL;
+  const long n = (long)D * H * W;
+  CENET_LAUNCH(border_gather_kernel<double>, dim3(edt_cdiv(n, CP_CHUNK)), dim3(256), stream, bl, match, n, H, W, offs, src, out);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
 }

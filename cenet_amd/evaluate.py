@@ -15,6 +15,8 @@ produces the masks and the overlap counts (loss_optim.hip).
     the few thousand distances is taken on the host, in float64 like numpy does.  `label_metrics` scores all classes of a
     volume from the two label maps at once; `method=` picks between the all-pairs minimum and the exact distance transform
     (edt.hip), which is linear in the voxels and so also handles the noise an untrained network predicts.
+    `spacing=` (medpy's `voxelspacing`, which the reference does not pass) reports hd95 / assd in the volume's physical unit
+    through fp64 forms of the same kernels; `nsd_tolerance=` / `surface_dice` add the normalised surface Dice.
 The scipy cubic `zoom` of slices that do not have the network's input size is the reference's own host-side dependency
 (metrics_eval.py:45,55); `resize="host"` (the default) calls it the same way, `resize="device"` runs both resizes on the device
 (csrc/volresize.hip through `predict_volume`: the volume is uploaded once and only the metric numbers come back).
@@ -23,6 +25,7 @@ The scipy cubic `zoom` of slices that do not have the network's input size is th
 """
 from __future__ import annotations
 
+import math
 from typing import Iterable, List, Sequence, Tuple
 
 import numpy as np
@@ -115,7 +118,11 @@ def surface_points(mask: torch.Tensor) -> torch.Tensor:
     return torch.nonzero(border).to(torch.int32).contiguous()
 
 
-def _directed_sq(a_pts: torch.Tensor, b_pts: torch.Tensor) -> torch.Tensor:
+def _directed_sq(a_pts: torch.Tensor, b_pts: torch.Tensor, spacing=None) -> torch.Tensor:
+    if spacing is not None:
+        out = torch.empty((a_pts.shape[0],), dtype=torch.float64, device=a_pts.device)
+        kern.min_sqdist_spaced(a_pts, b_pts, out, spacing)
+        return out
     out = torch.full((a_pts.shape[0],), 2 ** 31 - 1, dtype=torch.int32, device=a_pts.device)
     kern.min_sqdist(a_pts, b_pts, out)
     return out
@@ -127,6 +134,45 @@ _INT_MAX = 2 ** 31 - 1
 # two borders, the all-pairs kernel below that (DESIGN.md §9 has the scan behind the number: the two methods cross between 549 and
 # 741 pairs per box voxel on the MI355X, at about 640 by linear interpolation of the time differences)
 AUTO_PAIRS_PER_BOX_VOXEL = 640
+# the same threshold for the fp64 kernels a `spacing` selects: their all-pairs kernel is slower against its transform than the
+# integer one, so they cross earlier (profiles/volume_metrics_spacing.json: between 403 and 549 pairs per box voxel on
+# the MI355X, at 503 by linear interpolation of the time differences)
+AUTO_PAIRS_PER_BOX_VOXEL_SPACED = 500
+
+
+def _spacing(spacing, ndim: int):
+    """medpy's `voxelspacing` for an array of `ndim` (2 or 3) axes -> None, or (sz, sy, sx) as floats (an image: sz = 1.0, which no
+    distance within the one plane reads).  A number broadcasts; a sequence has one entry per axis, (z, y, x) or (y, x).  Anything
+    else, and an entry that is not positive and finite, raises ValueError."""
+    if spacing is None:
+        return None
+    what = f"spacing: a positive finite number or {ndim} of them ({'z, y, x' if ndim == 3 else 'y, x'}) expected, got {spacing!r}"
+    if isinstance(spacing, (str, bytes, dict, set)) or torch.is_tensor(spacing) and spacing.dim() > 1:
+        raise ValueError(what)
+    try:
+        sp = (float(spacing),) * ndim if np.ndim(spacing) == 0 else tuple(float(v) for v in spacing)
+    except (TypeError, ValueError):
+        raise ValueError(what) from None
+    if len(sp) != ndim or not all(0.0 < v < float("inf") for v in sp):
+        raise ValueError(what)
+    return (1.0,) * (3 - ndim) + sp
+
+
+def _tolerance(nsd_tolerance):
+    """None, or the NSD tolerance as a float; ValueError unless it is positive and finite"""
+    if nsd_tolerance is None:
+        return None
+    try:
+        tau = math.nan if isinstance(nsd_tolerance, (str, bytes)) else float(nsd_tolerance)
+    except (TypeError, ValueError):
+        raise ValueError(f"nsd tolerance: a positive finite number expected, got {nsd_tolerance!r}") from None
+    if not 0.0 < tau < float("inf"):
+        raise ValueError(f"nsd tolerance: a positive finite number expected, got {nsd_tolerance!r}")
+    return tau
+
+
+def _nsd(d1: np.ndarray, d2: np.ndarray, tau: float) -> float:
+    return float(np.count_nonzero(d1 <= tau) + np.count_nonzero(d2 <= tau)) / float(d1.size + d2.size)
 
 
 def _download(t: torch.Tensor) -> np.ndarray:
@@ -160,13 +206,16 @@ def _border_offsets(bl: torch.Tensor, c: int, n: int) -> torch.Tensor:
     return (torch.cumsum(counts, 0) - counts).to(torch.int32)
 
 
-def _surface_sq(blp: torch.Tensor, blg: torch.Tensor, tab: np.ndarray, todo: Sequence[int], method: str):
+def _surface_sq(blp: torch.Tensor, blg: torch.Tensor, tab: np.ndarray, todo: Sequence[int], method: str, spacing=None):
     """squared surface distances of the classes `todo` (both masks non-empty): {c: (pred border -> gt border, gt border -> pred
     border)} as int32 numpy arrays in C order of the border voxels.  Everything is queued without a synchronisation, sized from
-    the table; one download at the end brings all the arrays."""
+    the table; one download at the end brings all the arrays.  `spacing` (sz, sy, sx): the fp64 kernels, float64 arrays in the
+    spacing's unit squared."""
     if not todo:
         return {}
     dev = blp.device
+    per_voxel = AUTO_PAIRS_PER_BOX_VOXEL if spacing is None else AUTO_PAIRS_PER_BOX_VOXEL_SPACED
+    sq_t = torch.int32 if spacing is None else torch.float64
     plan, total, scratch = [], 0, 0
     for c in todo:
         row = [int(v) for v in tab[c]]
@@ -175,13 +224,15 @@ def _surface_sq(blp: torch.Tensor, blg: torch.Tensor, tab: np.ndarray, todo: Seq
         hi = [max(-row[8 + k], -row[14 + k]) for k in range(3)]
         box = [h - l + 1 for l, h in zip(lo, hi)]
         vol = box[0] * box[1] * box[2]
-        edt = method == "edt" or (method == "auto" and na * nb > AUTO_PAIRS_PER_BOX_VOXEL * vol and kern.edt_supported(*box))
+        edt = method == "edt" or (method == "auto" and na * nb > per_voxel * vol and kern.edt_supported(*box))
         plan.append((c, na, nb, lo, box, vol, edt, total))
         total += na + nb
         scratch = max(scratch, vol if edt else 0)
-    out = torch.full((total,), _INT_MAX, dtype=torch.int32, device=dev)
-    tmp = torch.empty(scratch, dtype=torch.int32, device=dev) if scratch else None
-    d2 = torch.empty(scratch, dtype=torch.int32, device=dev) if scratch else None
+    # (the integer all-pairs kernel merges into its output, which starts at INT_MAX; the fp64 kernels write theirs)
+    out = torch.full((total,), _INT_MAX, dtype=sq_t, device=dev) if spacing is None else torch.empty((total,), dtype=sq_t, device=dev)
+    tmp = torch.empty(scratch, dtype=sq_t, device=dev) if scratch else None
+    d2 = torch.empty(scratch, dtype=sq_t, device=dev) if scratch else None
+    xd = torch.empty(scratch, dtype=torch.int32, device=dev) if scratch and spacing is not None else None
     for c, na, nb, lo, box, vol, edt, off in plan:
         # the union bounding box of the two borders holds every query and every feature voxel, so the transform of the crop equals
         # the transform of the volume at every query voxel
@@ -189,7 +240,12 @@ def _surface_sq(blp: torch.Tensor, blg: torch.Tensor, tab: np.ndarray, todo: Seq
         b = blg[lo[0]:lo[0] + box[0], lo[1]:lo[1] + box[1], lo[2]:lo[2] + box[2]].contiguous()
         offs_a, offs_b = _border_offsets(a, c, vol), _border_offsets(b, c, vol)
         oa, ob = out[off:off + na], out[off + na:off + na + nb]
-        if edt:
+        if edt and spacing is not None:
+            kern.edt_sq_spaced_raw(b, c, xd, tmp, d2, *box, spacing)
+            kern.border_gather(a, c, *box, offs_a, d2, oa)
+            kern.edt_sq_spaced_raw(a, c, xd, tmp, d2, *box, spacing)
+            kern.border_gather(b, c, *box, offs_b, d2, ob)
+        elif edt:
             kern.edt_sq_raw(b, c, tmp, d2, *box)
             kern.border_gather(a, c, *box, offs_a, d2, oa)
             kern.edt_sq_raw(a, c, tmp, d2, *box)
@@ -199,8 +255,12 @@ def _surface_sq(blp: torch.Tensor, blg: torch.Tensor, tab: np.ndarray, todo: Seq
             pb = torch.empty((nb, 3), dtype=torch.int32, device=dev)
             kern.border_gather(a, c, *box, offs_a, None, pa)
             kern.border_gather(b, c, *box, offs_b, None, pb)
-            kern.min_sqdist(pa, pb, oa)
-            kern.min_sqdist(pb, pa, ob)
+            if spacing is not None:
+                kern.min_sqdist_spaced(pa, pb, oa, spacing)
+                kern.min_sqdist_spaced(pb, pa, ob, spacing)
+            else:
+                kern.min_sqdist(pa, pb, oa)
+                kern.min_sqdist(pb, pa, ob)
     arr = _download(out)
     return {c: (arr[off:off + na], arr[off + na:off + na + nb]) for c, na, nb, _, _, _, _, off in plan}
 
@@ -209,17 +269,26 @@ def _sqrt64(sq: np.ndarray) -> np.ndarray:
     return np.sqrt(sq.astype(np.float64))
 
 
-def label_metrics(pred: torch.Tensor, gt: torch.Tensor, classes: int, kind: str = "acdc", method: str = "auto"):
+def label_metrics(pred: torch.Tensor, gt: torch.Tensor, classes: int, kind: str = "acdc", method: str = "auto", spacing=None,
+                  nsd_tolerance=None):
     """The per-class metric loop of test_single_volume (metrics_eval.py:60-62, utils_synapse.py:80-82) from the two label
     volumes [D,H,W] (or images [H,W]) directly: [(dice, hd95, jaccard, assd)] (kind="acdc", calculate_metric_percase of
     metrics_eval.py:9-21) or [(dice, hd95)] (kind="synapse", utils_synapse.py:12-21) for classes 1..classes-1, with the
     reference's rules for empty masks.  One kernel pass yields every class's borders, counts and bounding boxes; two downloads per
-    volume (that table, then all the distance arrays) whatever `classes` is.  `method`: see `surface_distances`, chosen per class."""
+    volume (that table, then all the distance arrays) whatever `classes` is.  `method`: see `surface_distances`, chosen per class.
+    `spacing`: the voxel spacing as `surface_distances` takes it; hd95 and assd are then in its unit (millimetres), from the fp64
+    kernels, still with two downloads.  `nsd_tolerance` (a distance in that unit): every tuple gains the normalised surface Dice
+    of `surface_dice` as its LAST element, counted on the host from the same arrays.  Its rule for empty masks follows the
+    tuple's Dice rule, 1 for a prediction without ground truth and 0 otherwise: one more of the reference's odd family (a class
+    absent from both scores 0, a false positive scores 1), not a definition of its own."""
     assert kind in ("acdc", "synapse"), kind
     assert method in METHODS, method
+    if pred.dim() in (2, 3):  # (any other rank is refused by _label_table below)
+        spacing = _spacing(spacing, pred.dim())
+    tau = _tolerance(nsd_tolerance)
     blp, blg, tab = _label_table(pred, gt, classes)
     todo = [c for c in range(1, classes) if tab[c, 1] > 0 and tab[c, 2] > 0]
-    sq = _surface_sq(blp, blg, tab, todo, method)
+    sq = _surface_sq(blp, blg, tab, todo, method, spacing)
     res = []
     for c in range(1, classes):
         inter, np_, ng = (int(v) for v in tab[c, :3])
@@ -228,63 +297,91 @@ def label_metrics(pred: torch.Tensor, gt: torch.Tensor, classes: int, kind: str 
             dice = 2.0 * inter / float(np_ + ng)
             h95 = float(np.percentile(np.hstack((d1, d2)), 95))
             if kind == "acdc":
-                res.append((dice, h95, inter / float(np_ + ng - inter), float(np.mean((d1.mean(), d2.mean())))))
+                m = (dice, h95, inter / float(np_ + ng - inter), float(np.mean((d1.mean(), d2.mean()))))
             else:
-                res.append((dice, h95))
+                m = (dice, h95)
+            res.append(m if tau is None else m + (_nsd(d1, d2, tau),))
         elif np_ > 0 and ng == 0:
-            res.append((1, 0, 1, 0) if kind == "acdc" else (1, 0))
+            m = (1, 0, 1, 0) if kind == "acdc" else (1, 0)
+            res.append(m if tau is None else m + (1,))
         else:
-            res.append((0, 0, 0, 0) if kind == "acdc" else (0, 0))
+            m = (0, 0, 0, 0) if kind == "acdc" else (0, 0)
+            res.append(m if tau is None else m + (0,))
     return res
 
 
-def surface_distances(result: torch.Tensor, reference: torch.Tensor, method: str = "auto") -> Tuple[np.ndarray, np.ndarray]:
-    """Both directed surface-distance sets (result->reference, reference->result) as float64 arrays, unit voxel spacing.
-    Raises RuntimeError on an empty mask, as medpy does.  method="pairs": every border voxel against every border voxel of the
+def surface_distances(result: torch.Tensor, reference: torch.Tensor, method: str = "auto",
+                      spacing=None) -> Tuple[np.ndarray, np.ndarray]:
+    """Both directed surface-distance sets (result->reference, reference->result) as float64 arrays, in voxels (unit voxel
+    spacing) unless `spacing` is given.  Raises RuntimeError on an empty mask, as medpy does.  method="pairs": every border voxel against every border voxel of the
     other mask (metrics.hip); "edt": the exact distance transform of one border read at the other (edt.hip), over the union
-    bounding box of the two; "auto": whichever the sizes favour.  The arrays are identical either way."""
+    bounding box of the two; "auto": whichever the sizes favour.  The arrays are identical either way.
+    `spacing`: medpy's `voxelspacing` — a positive number for every axis, or one per array axis, (z, y, x) for a volume and (y, x)
+    for an image (ValueError for anything else): the distances are in its unit, from the fp64 forms of the same kernels.  Which
+    voxels are border voxels does not depend on it.  With a spacing the methods agree to rounding (a few units in the last place;
+    bit for bit when the spacings are dyadic), not necessarily in every bit: they sum the three terms in different orders."""
     assert method in METHODS, method
+    if result.dim() in (2, 3):
+        spacing = _spacing(spacing, result.dim())
+    elif spacing is not None:
+        raise ValueError(f"spacing: a volume [D,H,W] or an image [H,W] expected, got {tuple(result.shape)}")
     if method == "pairs" or (method == "auto" and (result.shape != reference.shape or result.dim() not in (2, 3))):
         ra, rb = surface_points(result), surface_points(reference)
         if ra.shape[0] == 0:
             raise RuntimeError("The first supplied array does not contain any binary object.")
         if rb.shape[0] == 0:
             raise RuntimeError("The second supplied array does not contain any binary object.")
-        d1 = _directed_sq(ra, rb).cpu().numpy().astype(np.float64)
-        d2 = _directed_sq(rb, ra).cpu().numpy().astype(np.float64)
+        d1 = _directed_sq(ra, rb, spacing).cpu().numpy().astype(np.float64)
+        d2 = _directed_sq(rb, ra, spacing).cpu().numpy().astype(np.float64)
         return np.sqrt(d1), np.sqrt(d2)
     blp, blg, tab = _label_table(result != 0, reference != 0, 2)
     if tab[1, 1] == 0:
         raise RuntimeError("The first supplied array does not contain any binary object.")
     if tab[1, 2] == 0:
         raise RuntimeError("The second supplied array does not contain any binary object.")
-    sq = _surface_sq(blp, blg, tab, [1], method)[1]
+    sq = _surface_sq(blp, blg, tab, [1], method, spacing)[1]
     return _sqrt64(sq[0]), _sqrt64(sq[1])
 
 
-def hd95(result: torch.Tensor, reference: torch.Tensor, method: str = "auto") -> float:
-    d1, d2 = surface_distances(result, reference, method)
+def hd95(result: torch.Tensor, reference: torch.Tensor, method: str = "auto", spacing=None) -> float:
+    d1, d2 = surface_distances(result, reference, method, spacing)
     return float(np.percentile(np.hstack((d1, d2)), 95))
 
 
-def assd(result: torch.Tensor, reference: torch.Tensor, method: str = "auto") -> float:
-    d1, d2 = surface_distances(result, reference, method)
+def assd(result: torch.Tensor, reference: torch.Tensor, method: str = "auto", spacing=None) -> float:
+    d1, d2 = surface_distances(result, reference, method, spacing)
     return float(np.mean((d1.mean(), d2.mean())))
 
 
-def metric_percase(pred: torch.Tensor, gt: torch.Tensor, method: str = "auto") -> Tuple[float, float, float, float]:
+def surface_dice(result: torch.Tensor, reference: torch.Tensor, tolerance: float, spacing=None, method: str = "auto") -> float:
+    """Normalised surface Dice (NSD) at `tolerance`: with d1, d2 the two arrays of `surface_distances(result, reference, method,
+    spacing)`, (|{d1 <= tolerance}| + |{d2 <= tolerance}|) / (|d1| + |d2|) — the share of border voxels of either mask that lie
+    within `tolerance` of the other mask's border.  The tolerance is in the unit of `spacing` (voxels without one) and must be
+    positive and finite (ValueError).  Raises RuntimeError on an empty mask, as `surface_distances` does.
+    This is the VOXEL-COUNT form: every border voxel weighs the same.  The surfel-area form of Nikolov et al. (2018), which weighs
+    each surface element by its physical area, is a different number on anisotropic volumes and is not computed here."""
+    tau = _tolerance(tolerance)
+    if tau is None:
+        raise ValueError("nsd tolerance: a positive finite number expected, got None")
+    d1, d2 = surface_distances(result, reference, method, spacing)
+    return _nsd(d1, d2, tau)
+
+
+def metric_percase(pred: torch.Tensor, gt: torch.Tensor, method: str = "auto", spacing=None) -> Tuple[float, float, float, float]:
     """calculate_metric_percase (metrics_eval.py:9-21): (dice, hd95, jaccard, assd) of two binary volumes, with its rules
-    for empty masks."""
+    for empty masks.  `spacing`: as `surface_distances` takes it."""
     assert method in METHODS, method
     if method != "pairs" and pred.shape == gt.shape and pred.dim() in (2, 3):
-        return label_metrics(pred != 0, gt != 0, 2, "acdc", method)[0]
+        return label_metrics(pred != 0, gt != 0, 2, "acdc", method, spacing)[0]
+    if pred.dim() in (2, 3):
+        _spacing(spacing, pred.dim())  # (refused here, whatever the masks hold; surface_distances reads it again)
     p, g = pred != 0, gt != 0
     np_, ng = int(p.sum()), int(g.sum())
     if np_ > 0 and ng > 0:
         inter = int((p & g).sum())
         dice = 2.0 * inter / float(np_ + ng)
         jac = inter / float(np_ + ng - inter)
-        d1, d2 = surface_distances(p, g, method)
+        d1, d2 = surface_distances(p, g, method, spacing)
         return dice, float(np.percentile(np.hstack((d1, d2)), 95)), jac, float(np.mean((d1.mean(), d2.mean())))
     if np_ > 0 and ng == 0:
         return 1, 0, 1, 0
@@ -556,11 +653,25 @@ def _predict_volume_tta(net, volume, patch, batch_slices, normalize, labels, tta
     return pred, total
 
 
+def _surface_kwargs(spacing, nsd_tolerance, ndim: int) -> dict:
+    """what the volume wrappers add to their `label_metrics` call: nothing for (None, None), so that call is then the one it has
+    always been; both are checked here, before the network runs"""
+    _spacing(spacing, ndim)
+    _tolerance(nsd_tolerance)
+    kw = {}
+    if spacing is not None:
+        kw["spacing"] = spacing
+    if nsd_tolerance is not None:
+        kw["nsd_tolerance"] = nsd_tolerance
+    return kw
+
+
 @torch.no_grad()
 def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int] = (224, 224), batch_slices: int = 32,
                        device=None, resize: str = "host", test_save_path=None, case=None,
                        z_spacing: float = 1.0, postprocess=None, lcc_connectivity: int = 1,
-                       lcc_per_slice: bool = False, tta=None) -> List[Tuple[float, float, float, float]]:
+                       lcc_per_slice: bool = False, tta=None, spacing=None,
+                       nsd_tolerance=None) -> List[Tuple[float, float, float, float]]:
     """test_single_volume (metrics_eval.py:37-84) for a 3-D volume: image / label [1,D,H,W] or [D,H,W] (tensor or ndarray).
     Slices are resized to `patch_size` with scipy's cubic zoom and the predictions back with order 0 exactly as the
     reference does (host side), but the network runs on batches of slices and the metrics on the device.
@@ -570,10 +681,14 @@ def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int
     the device before it is scored and saved (not in the reference; None: no such step).
     `tta` (a name of TTA_SETS or a tuple of view codes): test-time augmentation inside `predict_volume`, before `postprocess`;
     it needs resize="device" and a case the device resize takes, and raises ValueError otherwise.
+    `spacing`: the volume's voxel spacing, a number or (z, y, x), in which hd95 and assd are then reported (`label_metrics`; None:
+    voxels, as the reference).  `z_spacing` is not read for it: it only goes into the side-car file of `test_save_path`.
+    `nsd_tolerance`: every tuple gains the normalised surface Dice at that tolerance as its last element.
     Returns [(dice, hd95, jaccard, assd)] for classes 1..classes-1."""
     from scipy.ndimage import zoom
     assert resize in ("host", "device"), resize
     _check_postprocess(postprocess)
+    surf = _surface_kwargs(spacing, nsd_tolerance, 3)
     device = device or next(net.parameters()).device
     net.eval()
     on_dev = _device_case(image, label, device, patch_size) if resize == "device" else None
@@ -583,7 +698,7 @@ def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int
         pred_d = _postprocessed(pred_d, classes, postprocess, lcc_connectivity, lcc_per_slice)
         if test_save_path is not None:
             _save_case(test_save_path, case, z_spacing, pred_d, on_dev[0], on_dev[1])
-        return label_metrics(pred_d, on_dev[1], classes, "acdc")
+        return label_metrics(pred_d, on_dev[1], classes, "acdc", **surf)
     image = image.squeeze(0).cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
     label = label.squeeze(0).cpu().numpy() if torch.is_tensor(label) else np.asarray(label)
     assert image.ndim == 3, "volume [D,H,W] expected"
@@ -607,23 +722,25 @@ def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int
         pred_d = prediction = _postprocessed(pred_d, classes, postprocess, lcc_connectivity, lcc_per_slice)
     if test_save_path is not None:
         _save_case(test_save_path, case, z_spacing, prediction, image, label)
-    return label_metrics(pred_d, lab_d, classes, "acdc")
+    return label_metrics(pred_d, lab_d, classes, "acdc", **surf)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # Synapse (utils/utils_synapse.py:12-100) and skin (utils/utils_skin.py:97-170) evaluation wrappers
 # ---------------------------------------------------------------------------------------------------------------------------
-def synapse_metric_percase(pred: torch.Tensor, gt: torch.Tensor, method: str = "auto") -> Tuple[float, float]:
+def synapse_metric_percase(pred: torch.Tensor, gt: torch.Tensor, method: str = "auto", spacing=None) -> Tuple[float, float]:
     """calculate_metric_percase of utils_synapse.py:12-21: (dice, hd95) of two binary volumes; (1, 0) for a prediction without
-    ground truth, (0, 0) otherwise."""
+    ground truth, (0, 0) otherwise.  `spacing`: as `surface_distances` takes it."""
     assert method in METHODS, method
     if method != "pairs" and pred.shape == gt.shape and pred.dim() in (2, 3):
-        return label_metrics(pred != 0, gt != 0, 2, "synapse", method)[0]
+        return label_metrics(pred != 0, gt != 0, 2, "synapse", method, spacing)[0]
+    if pred.dim() in (2, 3):
+        _spacing(spacing, pred.dim())  # (refused here, whatever the masks hold; surface_distances reads it again)
     p, g = pred != 0, gt != 0
     np_, ng = int(p.sum()), int(g.sum())
     if np_ > 0 and ng > 0:
         inter = int((p & g).sum())
-        d1, d2 = surface_distances(p, g, method)
+        d1, d2 = surface_distances(p, g, method, spacing)
         return 2.0 * inter / float(np_ + ng), float(np.percentile(np.hstack((d1, d2)), 95))
     if np_ > 0 and ng == 0:
         return 1, 0
@@ -633,7 +750,8 @@ def synapse_metric_percase(pred: torch.Tensor, gt: torch.Tensor, method: str = "
 @torch.no_grad()
 def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequence[int] = (256, 256), test_save_path=None,
                                case=None, z_spacing: float = 1.0, batch_slices: int = 32, device=None, resize: str = "host",
-                               postprocess=None, lcc_connectivity: int = 1, lcc_per_slice: bool = False, tta=None):
+                               postprocess=None, lcc_connectivity: int = 1, lcc_per_slice: bool = False, tta=None,
+                               spacing=None, nsd_tolerance=None):
     """test_single_volume of utils_synapse.py:49-97: every slice of the volume [1, D, H, W] is resized to `patch_size` (cubic
     zoom), normalised with Normalize([0.5], [0.5]) (`ToTensor` leaves float arrays unscaled), classified, and the prediction
     resized back with order 0; returns [(dice, hd95)] for classes 1..classes-1.  A 2-D input takes the reference's second branch
@@ -641,10 +759,14 @@ def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequ
     the metrics run on the device.  `test_save_path` (NIfTI files through SimpleITK, which is absent here) writes .npy volumes
     with the spacing (1, 1, z_spacing) in a side-car text file instead.  `resize="device"`: as for `test_single_volume`, with the
     normalisation inside the resize kernel; the 2-D branch has no resize and is the same in both modes.  `postprocess`,
-    `lcc_connectivity`, `lcc_per_slice`, `tta`: as for `test_single_volume` (the 2-D branch takes no `tta`: ValueError)."""
+    `lcc_connectivity`, `lcc_per_slice`, `tta`: as for `test_single_volume` (the 2-D branch takes no `tta`: ValueError).
+    `spacing` (a number, or one entry per axis of the input: (z, y, x), or (y, x) for the 2-D branch) and `nsd_tolerance`: as for
+    `test_single_volume`; the tuples are then (dice, hd95 in that unit[, nsd]).  `z_spacing` stays the side-car's alone."""
     from scipy.ndimage import zoom
     assert resize in ("host", "device"), resize
     _check_postprocess(postprocess)
+    nd = (image.squeeze(0) if torch.is_tensor(image) else np.asarray(image)).ndim
+    surf = _surface_kwargs(spacing, nsd_tolerance, nd if nd in (2, 3) else 3)
     device = device or next(net.parameters()).device
     net.eval()
     on_dev = _device_case(image, label, device, patch_size) if resize == "device" else None
@@ -654,7 +776,7 @@ def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequ
         pred_d = _postprocessed(pred_d, classes, postprocess, lcc_connectivity, lcc_per_slice)
         if test_save_path is not None:
             _save_case(test_save_path, case, z_spacing, pred_d, on_dev[0], on_dev[1])
-        return label_metrics(pred_d, on_dev[1], classes, "synapse")
+        return label_metrics(pred_d, on_dev[1], classes, "synapse", **surf)
     image = image.squeeze(0).cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
     label = label.squeeze(0).cpu().numpy() if torch.is_tensor(label) else np.asarray(label)
     if image.ndim == 3:
@@ -681,7 +803,7 @@ def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequ
     lab_d = torch.from_numpy(np.ascontiguousarray(label)).to(device)
     if postprocess is not None:
         pred_d = prediction = _postprocessed(pred_d, classes, postprocess, lcc_connectivity, lcc_per_slice)
-    metric_list = label_metrics(pred_d, lab_d, classes, "synapse")
+    metric_list = label_metrics(pred_d, lab_d, classes, "synapse", **surf)
     if test_save_path is not None:
         _save_case(test_save_path, case, z_spacing, prediction, image, label)
     return metric_list
@@ -720,21 +842,39 @@ def val_single_volume(image, label, net, classes: int, patch_size: Sequence[int]
 @torch.no_grad()
 def inference(net, volumes, classes: int, patch_size: Sequence[int] = (224, 224), z_spacing: float = 1.0, test_save_path=None,
               log=print, resize: str = "device", batch_slices: int = 32, device=None, postprocess=None,
-              lcc_connectivity: int = 1, lcc_per_slice: bool = False, tta=None) -> Tuple[float, float]:
+              lcc_connectivity: int = 1, lcc_per_slice: bool = False, tta=None, spacing=None,
+              nsd_tolerance=None) -> Tuple[float, float]:
     """inference (utils_acdc.py:7-33): `test_single_volume` for every case of `volumes` (the test loader's dicts: `image`
     [1, D, H, W], `label`, `case_name` — a string or the DataLoader's one-element list), the reference's per-case and per-class
     log lines through `log`, and (mean dice, mean hd95): the metric table averaged over the cases, then over the classes.
-    `postprocess`, `lcc_connectivity`, `lcc_per_slice` and `tta` go to `test_single_volume`."""
+    `postprocess`, `lcc_connectivity`, `lcc_per_slice` and `tta` go to `test_single_volume`.
+    `spacing`: the voxel spacing hd95 and assd are reported in — a number or (z, y, x) for all cases, or one per case: a dict
+    {case_name: spacing}, which must hold every case, or a list with one spacing per case in the order of `volumes` (a list of
+    three NUMBERS is one spacing for all cases).  `nsd_tolerance`: the tables gain the normalised surface Dice as a fifth column,
+    one more log line reports its means, and the result is (mean dice, mean hd95, mean nsd)."""
     _check_postprocess(postprocess)
+    _tolerance(nsd_tolerance)
+    per_case = isinstance(spacing, dict) or (isinstance(spacing, (list, tuple)) and any(np.ndim(v) > 0 or v is None for v in spacing))
+    if not per_case:
+        _spacing(spacing, 3)
     post = {} if postprocess is None else dict(postprocess=postprocess, lcc_connectivity=lcc_connectivity,
                                                lcc_per_slice=lcc_per_slice)
     if tta is not None:
         post["tta"] = tta
+    if nsd_tolerance is not None:
+        post["nsd_tolerance"] = nsd_tolerance
     net.eval()
     total, n = 0.0, 0
     for i, batch in enumerate(volumes):
         case = batch["case_name"]
         case = case[0] if isinstance(case, (list, tuple)) else case
+        if per_case:
+            try:
+                post["spacing"] = spacing[case] if isinstance(spacing, dict) else spacing[i]
+            except (KeyError, IndexError):
+                raise ValueError(f"inference: no spacing for case {case!r} (index {i})") from None
+        elif spacing is not None:
+            post["spacing"] = spacing
         m = test_single_volume(batch["image"], batch["label"], net, classes, patch_size=patch_size, batch_slices=batch_slices,
                                device=device, resize=resize, test_save_path=test_save_path, case=case, z_spacing=z_spacing,
                                **post)
@@ -746,9 +886,14 @@ def inference(net, volumes, classes: int, patch_size: Sequence[int] = (224, 224)
         raise ValueError("inference: no test volumes")
     table = total / n
     for c in range(1, classes):
-        log("Mean class (%d) mean_dice %f mean_hd95 %f, mean_jacard %f mean_asd %f" % ((c,) + tuple(table[c - 1])))
+        log("Mean class (%d) mean_dice %f mean_hd95 %f, mean_jacard %f mean_asd %f" % ((c,) + tuple(table[c - 1][:4])))
     performance, mean_hd95 = float(np.mean(table, axis=0)[0]), float(np.mean(table, axis=0)[1])
     log("Testing performance in best val model) mean_dice:%f mean_hd95:%f" % (performance, mean_hd95))
+    if nsd_tolerance is not None:
+        mean_nsd = float(np.mean(table, axis=0)[4])
+        log("mean_nsd at tolerance %g per class: %s mean_nsd:%f" % (float(nsd_tolerance), " ".join("%f" % v for v in table[:, 4]),
+                                                                    mean_nsd))
+        return performance, mean_hd95, mean_nsd
     return performance, mean_hd95
 
 

@@ -992,6 +992,49 @@ def edt_sq(feat_u8: torch.Tensor) -> torch.Tensor:
     return d2
 
 
+def check_spacing3(spacing):
+    """(sz, sy, sx) as floats; ValueError unless it holds three positive finite numbers"""
+    try:
+        sp = tuple(float(v) for v in spacing)
+    except (TypeError, ValueError):
+        raise ValueError(f"spacing: three positive finite numbers (z, y, x) expected, got {spacing!r}") from None
+    if len(sp) != 3 or not all(0.0 < v < math.inf for v in sp):
+        raise ValueError(f"spacing: three positive finite numbers (z, y, x) expected, got {spacing!r}")
+    return sp
+
+
+def edt_sq_spaced_raw(feat_u8, match, xd_i32, tmp_f64, d2_f64, D, H, W, spacing):
+    """cenet_edt_sq_spaced_u8 without the feature check: d2 = +inf everywhere when no voxel of feat_u8 is a feature"""
+    if not edt_supported(D, H, W):
+        raise ValueError(f"the distance transform needs D^2 + H^2 + W^2 < 2^31, got {(D, H, W)}")
+    _call("cenet_edt_sq_spaced_u8", feat_u8, match, xd_i32, tmp_f64, d2_f64, D, H, W, *check_spacing3(spacing))
+
+
+def edt_sq_spaced(feat_u8: torch.Tensor, spacing) -> torch.Tensor:
+    """exact squared Euclidean distance transform with a voxel spacing: feat_u8 [D,H,W] uint8 (non-zero = feature voxel),
+    spacing (sz, sy, sx) -> float64 [D,H,W], d2[v] = min over feature voxels f of sz^2 (vz-fz)^2 + sy^2 (vy-fy)^2 + sx^2 (vx-fx)^2
+    (scipy: distance_transform_edt(~feat, sampling=spacing)^2).  A volume without a feature voxel is refused."""
+    assert feat_u8.dim() == 3, "[D,H,W] expected"
+    spacing = check_spacing3(spacing)
+    feat_u8 = feat_u8.contiguous()
+    if not bool(feat_u8.any()):
+        raise ValueError("edt_sq_spaced: the volume has no feature voxel")
+    d2 = torch.empty(feat_u8.shape, dtype=torch.float64, device=feat_u8.device)
+    xd = torch.empty(feat_u8.shape, dtype=torch.int32, device=feat_u8.device)
+    edt_sq_spaced_raw(feat_u8, -1, xd, torch.empty_like(d2), d2, *feat_u8.shape, spacing)
+    return d2
+
+
+def min_sqdist_spaced(a_i32, b_i32, out_f64, spacing):
+    """out[i] = min_j of the squared distance between the voxels a_i and b_j ([n,3] int32 (z, y, x) rows) under `spacing`; out is
+    written, not merged into.  No atomics: a split of b goes through a scratch of partial minima allocated here."""
+    sp = check_spacing3(spacing)
+    na, nb = a_i32.shape[0], b_i32.shape[0]
+    n = int(_lib.lib().cenet_min_sqdist_spaced_ws_doubles(na, nb))
+    ws = torch.empty(n, dtype=torch.float64, device=out_f64.device) if n else None
+    _call("cenet_min_sqdist_spaced_f64", a_i32, na, b_i32, nb, *sp, ws, n, out_f64)
+
+
 def label_borders(pred_f32, gt_f32, border_pred_u8, border_gt_u8, table_i32, K, D, H, W, zfaces=True):
     _call("cenet_label_borders_f32", pred_f32, gt_f32, border_pred_u8, border_gt_u8, table_i32, K, D, H, W, bool(zfaces))
 
@@ -1000,9 +1043,13 @@ def border_count(bl_u8, match, n, counts_i32):
     _call("cenet_border_count_u8", bl_u8, match, n, counts_i32)
 
 
-def border_gather(bl_u8, match, D, H, W, offs_i32, src_i32, out_i32):
-    """src_i32 None: out gets the (z, y, x) rows of the matching voxels; else src at those voxels — both in C order"""
-    _call("cenet_border_gather_i32", bl_u8, match, D, H, W, offs_i32, src_i32, out_i32)
+def border_gather(bl_u8, match, D, H, W, offs_i32, src, out):
+    """src None: out (int32) gets the (z, y, x) rows of the matching voxels; else src at those voxels — both in C order.  src and
+    out are int32, or float64 (the spaced transform's values)"""
+    if src is not None and src.dtype == torch.float64:
+        _call("cenet_border_gather_f64", bl_u8, match, D, H, W, offs_i32, src, out)
+    else:
+        _call("cenet_border_gather_i32", bl_u8, match, D, H, W, offs_i32, src, out)
 
 
 def ccl_supported(D, H, W) -> bool:

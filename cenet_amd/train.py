@@ -48,7 +48,8 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
                log: Callable[[str], None] = print, optimizer: str = "sgd", scheduler: str = "poly",
                test_volumes: Optional[Callable[[], Iterable]] = None, save_dir: Optional[str] = None, img_size: int = 224,
                test_resize: str = "device", dice_class_weights=None, ce_class_weights=None, ignore_index=None,
-               test_postprocess=None, dist_weight_schedule: Optional[Callable[[int], tuple]] = None, test_tta=None) -> dict:
+               test_postprocess=None, dist_weight_schedule: Optional[Callable[[int], tuple]] = None, test_tta=None,
+               test_spacing=None, test_nsd_tolerance=None) -> dict:
     """main_acdc.py:200-290.  tr_loader yields {'image' [B,C,H,W] float (C = the network's input channels), 'label' [B,H,W]} batches (host or device tensors);
     val_batches() yields (image [1,1,H,W], label [1,H,W]) pairs for the per-epoch validation (main_acdc.py:218-231).
     optimizer / scheduler: the reference's --optimizer / --scheduler strings (main_acdc.py:34-35, core.py:12-41); `momentum`
@@ -56,7 +57,9 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
     test_volumes() yields the test loader's dicts (`image` [1,D,H,W], `label`, `case_name`) and needs val_batches: after an
     epoch whose validation Dice is >= the best so far, evaluate.inference runs over them (slices resized to img_size, `test_resize`
     as evaluate.test_single_volume takes it, `test_postprocess` as its `postprocess`: None or "lcc", `test_tta` as its `tta`: None, a name of evaluate.TTA_SETS or a tuple of view codes,
-    with test_resize="device" only); only when its Dice is >= the best test Dice do BOTH bests move and `best.pth` is
+    with test_resize="device" only, `test_spacing` / `test_nsd_tolerance` as its `spacing` / `nsd_tolerance`: the voxel spacing in
+    which te_HD95 is then reported, for all cases or per case, and the tolerance of the normalised surface Dice, which adds
+    'test_nsd' to the result); only when its Dice is >= the best test Dice do BOTH bests move and `best.pth` is
     written (main_acdc.py:272-278: a validation gain without a test gain moves neither); the last epoch writes
     `epoch=<e>_lr=<lr>_avg_dcs=<last test dice>.pth` (:286-289).  Files go to save_dir (None: none are written).
     -> {'loss': per-iteration losses read back at log points, 'epoch_loss': [...], 'val_dice': [...], 'lr': [...]} and, with
@@ -157,10 +160,15 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
             continue
         vl = hist["val_dice"][-1]
         if vl >= best_val:
-            te_dice, te_hd = evaluate.inference(net, test_volumes(), num_classes, patch_size=(img_size, img_size), log=log,
-                                                resize=test_resize,
-                                                **({} if test_postprocess is None else {"postprocess": test_postprocess}),
-                                                **({} if test_tta is None else {"tta": test_tta}))
+            te = evaluate.inference(net, test_volumes(), num_classes, patch_size=(img_size, img_size), log=log,
+                                    resize=test_resize,
+                                    **({} if test_postprocess is None else {"postprocess": test_postprocess}),
+                                    **({} if test_tta is None else {"tta": test_tta}),
+                                    **({} if test_spacing is None else {"spacing": test_spacing}),
+                                    **({} if test_nsd_tolerance is None else {"nsd_tolerance": test_nsd_tolerance}))
+            te_dice, te_hd = te[:2]
+            if test_nsd_tolerance is not None:
+                hist.setdefault("test_nsd", []).append(te[2])
             net.train()
             if te_dice >= best_test:
                 best_val, best_test = vl, te_dice

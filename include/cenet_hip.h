@@ -595,6 +595,26 @@ int cenet_label_borders_f32(const float* pred, const float* gt, unsigned char* b
 int cenet_border_count_u8(const unsigned char* bl, int match, long n, int* counts, cenet_stream_t stream);
 int cenet_border_gather_i32(const unsigned char* bl, int match, int D, int H, int W, const int* offs, const int* src, int* out,
                             cenet_stream_t stream);
+/* The surface distances with a voxel spacing (sz, sy, sx), in fp64 (medpy's `voxelspacing`, scipy's `sampling`):
+ * d2[v] = min over feature voxels f of sz^2 (vz-fz)^2 + sy^2 (vy-fy)^2 + sx^2 (vx-fx)^2.
+ * cenet_edt_sq_spaced_u8: the transform of cenet_edt_sq_u8 with that metric.  xd: D*H*W int32 of scratch (the integer x pass), tmp
+ * and d2: D*H*W doubles each; the result is in d2, +inf everywhere when there is no feature voxel.  With sy == sx the y pass is the
+ * integer one too and the value is sz^2 dz^2 + sx^2 (dy^2 + dx^2), else sz^2 dz^2 + (sy^2 dy^2 + sx^2 dx^2).  Every product and sum is exact
+ * when the spacings are dyadic and the volume small enough for 53 bits; no atomics, the same bits on every run.
+ * cenet_min_sqdist_spaced_f64: the all-pairs minimum of cenet_min_sqdist_i32 with that metric, the three terms summed as
+ * (z + y) + x; out [na] doubles, written (not merged into).  No atomics: the slices of b write partial minima into ws
+ * (ws_doubles >= cenet_min_sqdist_spaced_ws_doubles(na, nb) doubles, which is 0 when b is not split: ws may be NULL then) and a
+ * second launch takes their minimum.
+ * cenet_border_gather_f64: cenet_border_gather_i32 for a source of doubles (src must not be NULL).
+ * CENET_EINVAL (nothing launched) for a spacing that is not positive and finite (or whose square is not), and for the shapes the
+ * unspaced entry points refuse. */
+int cenet_edt_sq_spaced_u8(const unsigned char* feat, int match, int* xd, double* tmp, double* d2, int D, int H, int W, double sz,
+                           double sy, double sx, cenet_stream_t stream);
+long cenet_min_sqdist_spaced_ws_doubles(int na, int nb);
+int cenet_min_sqdist_spaced_f64(const int* a, int na, const int* b, int nb, double sz, double sy, double sx, double* ws,
+                                long ws_doubles, double* out, cenet_stream_t stream);
+int cenet_border_gather_f64(const unsigned char* bl, int match, int D, int H, int W, const int* offs, const double* src,
+                            double* out, cenet_stream_t stream);
 /* Connected components of a label volume (csrc/ccl.hip; a post-processing step, not in the reference).  labels [D,H,W]: class ids
  * as float, anything that is not an integer in [1, K) is background.  Two voxels are linked when they are neighbours and carry the
  * same class; connectivity 1 / 2 / 3 = 6 / 18 / 26 neighbours (scipy.ndimage.generate_binary_structure(3, connectivity)), zlinks

@@ -15,7 +15,14 @@ blob labels, under the parent's per-class `metric_percase(method="pairs")` loop,
 behind `evaluate.AUTO_PAIRS_PER_BOX_VOXEL`: two overlapping balls of growing radius under both methods.  Prints one JSON line.
 --tta NAME adds a third mode, `device_tta`: resize="device" with that view set of evaluate.TTA_SETS (its split has `tta_views`, and
 `resize_back` is the fused merge).
-    python tools/volume_infer.py [--bf16] [--only acdc|synapse] [--metrics pairs|edt|auto] [--metrics-cap 5e10] [--report] [--tta NAME]"""
+--spacing Z Y X scores in that voxel spacing (hd95 / assd in its unit, the fp64 kernels of csrc/edt.hip), --nsd TAU adds the
+normalised surface Dice at that tolerance.  With --spacing, --report is the SPACED report instead (`spaced_report`, written to
+--report-out as well, profiles/volume_metrics_spacing.json): per volume the spaced transform and the spaced `label_metrics` beside
+the unit-spacing path on the same volume and box (median of --reps runs), the host route they replace (download, then scipy's
+`distance_transform_edt(sampling=)` per class and direction; median of --host-reps), and the crossover scan behind
+`evaluate.AUTO_PAIRS_PER_BOX_VOXEL_SPACED` with its interpolated crossing.
+    python tools/volume_infer.py [--bf16] [--only acdc|synapse] [--metrics pairs|edt|auto] [--metrics-cap 5e10] [--report] [--tta NAME]
+                                 [--spacing Z Y X] [--nsd TAU] [--reps 20] [--host-reps 3] [--report-out PATH]"""
 import argparse
 import json
 import os
@@ -66,10 +73,14 @@ class Parts:
         return timed
 
 
+SURFACE = {}  # spacing= / nsd_tolerance= of --spacing / --nsd, handed to test_single_volume
+
+
 def call(net, image, label, mode, dev, tta=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    m = evaluate.test_single_volume(image, label, net, K, patch_size=PATCH, batch_slices=32, device=dev, resize=mode, tta=tta)
+    m = evaluate.test_single_volume(image, label, net, K, patch_size=PATCH, batch_slices=32, device=dev, resize=mode, tta=tta,
+                                    **SURFACE)
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3, m
 
@@ -169,6 +180,98 @@ def metrics_report(net, dev, cap, only):
     return rep
 
 
+def _ball_pair(dev, r, D=160, H=256, W=256):
+    """the crossover scan's two overlapping balls of radius r, and (na, nb, union box) from label_metrics' own table"""
+    zz, yy, xx = np.ogrid[:D, :H, :W]
+    a = ((zz - 80) ** 2 + (yy - 128) ** 2 + (xx - 120) ** 2 <= r * r).astype(np.float32)
+    b = ((zz - 80) ** 2 + (yy - 128) ** 2 + (xx - 120 - max(1, r // 4)) ** 2 <= r * r).astype(np.float32)
+    ta, tb = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
+    _, _, tab = evaluate._label_table(ta, tb, 2)
+    row = [int(v) for v in tab[1]]
+    box = [max(-row[8 + k], -row[14 + k]) - min(row[5 + k], row[11 + k]) + 1 for k in range(3)]
+    return ta, tb, row[3], row[4], box
+
+
+def host_route(pred, lab, classes, spacing):
+    """what a user did without `spacing=`: download both label maps, then medpy's algorithm on scipy per class and direction"""
+    p, g = pred.cpu().numpy(), lab.cpu().numpy()
+    out = []
+    for c in range(1, classes):
+        if (p == c).any() and (g == c).any():
+            d1 = O.surface_distances(p == c, g == c, voxelspacing=spacing)
+            d2 = O.surface_distances(g == c, p == c, voxelspacing=spacing)
+            out.append((float(np.percentile(np.hstack((d1, d2)), 95)), float(np.mean((d1.mean(), d2.mean())))))
+        else:
+            out.append((0.0, 0.0))
+    return out
+
+
+def timed_host(fn, reps):
+    runs = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        runs.append((time.perf_counter() - t0) * 1e3)
+        print(f"  host route run: {runs[-1]:.0f} ms", file=sys.stderr, flush=True)
+    return {"median": round(statistics.median(runs), 3), "spread": round(max(runs) - min(runs), 3), "runs": [round(v, 3) for v in runs]}
+
+
+def spaced_report(net, dev, only, spacing, nsd, reps, host_reps):
+    """the metrics alone with a voxel spacing, beside the unit-spacing path and the host route"""
+    rep = {"spacing": list(spacing), "nsd_tolerance": nsd, "reps": reps, "host_reps": host_reps, "volumes": {}, "crossover": []}
+    for name, shape in VOLUMES.items():
+        if only and name != only:
+            continue
+        print(f"spaced report: {name}", file=sys.stderr, flush=True)
+        image, label = make_volume(shape, seed=sum(shape))
+        lab = label[0].to(dev)
+        net_pred, _ = evaluate.predict_volume(net, image[0].to(dev), PATCH)
+        noise = torch.from_numpy(np.random.default_rng(1).integers(0, K, shape).astype(np.float32)).to(dev)
+        # the transform alone, whole volume: the labels' class-1 border as the feature set
+        _, blg, _ = evaluate._label_table(lab, lab, K)
+        n = blg.numel()
+        ti, di = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+        tf, df = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(2))
+        general = (spacing[0], spacing[1], spacing[2] * 1.0009765625)  # sy != sx: the fp64 y pass as well
+        rep["volumes"][f"{name}/transform"] = {
+            "shape": list(shape),
+            "unit_int32": timed(lambda: kern.edt_sq_raw(blg, 1, ti, di, *shape), reps),
+            "spaced_fp64": timed(lambda: kern.edt_sq_spaced_raw(blg, 1, ti, tf, df, *shape, spacing), reps),
+            "spaced_fp64_sy_ne_sx": timed(lambda: kern.edt_sq_spaced_raw(blg, 1, ti, tf, df, *shape, general), reps)}
+        del ti, di, tf, df
+        for tag, pred in (("net_pred", net_pred), ("noise_pred", noise)):
+            pairs, nbp, nbg = border_pairs(pred, lab, K)
+            e = {"shape": list(shape), "classes": K, "max_border_pairs": pairs, "border_voxels_pred": nbp, "border_voxels_gt": nbg}
+            e["edt_unit"] = timed(lambda: evaluate.label_metrics(pred, lab, K, method="edt"), reps)
+            e["edt_spaced"] = timed(lambda: evaluate.label_metrics(pred, lab, K, method="edt", spacing=spacing, nsd_tolerance=nsd), reps)
+            e["auto_spaced"] = timed(lambda: evaluate.label_metrics(pred, lab, K, method="auto", spacing=spacing, nsd_tolerance=nsd), reps)
+            if tag == "net_pred" and host_reps > 0:
+                e["host_scipy"] = timed_host(lambda: host_route(pred, lab, K, spacing), host_reps)
+                want = host_route(pred, lab, K, spacing)
+                got = evaluate.label_metrics(pred, lab, K, method="edt", spacing=spacing)
+                e["max_rel_diff_to_host"] = max(abs(g[k] - w[j]) / max(w[j], 1e-300) for g, w in zip(got, want)
+                                                for k, j in ((1, 0), (3, 1)) if w[j] > 0)
+            rep["volumes"][f"{name}/{tag}"] = e
+    if not only:
+        for r in (3, 6, 12, 24, 36, 48, 64, 72, 84):
+            ta, tb, na, nb, box = _ball_pair(dev, r)
+            vol = box[0] * box[1] * box[2]
+            p = timed(lambda: evaluate.label_metrics(ta, tb, 2, method="pairs", spacing=spacing), reps)
+            e = timed(lambda: evaluate.label_metrics(ta, tb, 2, method="edt", spacing=spacing), reps)
+            rep["crossover"].append({"radius": r, "na": na, "nb": nb, "box": box, "pairs_per_box_voxel": round(na * nb / vol, 2),
+                                     "pairs_ms": p["median"], "pairs_spread": p["spread"], "edt_ms": e["median"], "edt_spread": e["spread"]})
+        # the crossing: linear interpolation of (pairs - edt) between the last row where pairs wins and the next
+        rows = rep["crossover"]
+        rep["crossing_pairs_per_box_voxel"] = None
+        for lo, hi in zip(rows, rows[1:]):
+            dl, dh = lo["pairs_ms"] - lo["edt_ms"], hi["pairs_ms"] - hi["edt_ms"]
+            if dl <= 0 < dh:
+                x0, x1 = lo["pairs_per_box_voxel"], hi["pairs_per_box_voxel"]
+                rep["crossing_pairs_per_box_voxel"] = round(x0 + (x1 - x0) * (-dl) / (dh - dl), 1)
+    rep["auto_pairs_per_box_voxel_spaced"] = evaluate.AUTO_PAIRS_PER_BOX_VOXEL_SPACED
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bf16", action="store_true")
@@ -178,7 +281,18 @@ def main():
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--tta", choices=sorted(evaluate.TTA_SETS), default=None,
                     help="also time resize='device' with this test-time augmentation set (entry `device_tta`)")
+    ap.add_argument("--spacing", type=float, nargs=3, metavar=("Z", "Y", "X"), default=None,
+                    help="voxel spacing: hd95 / assd in its unit; with --report: the spaced report")
+    ap.add_argument("--nsd", type=float, default=None, help="tolerance of the normalised surface Dice (the unit of --spacing)")
+    ap.add_argument("--reps", type=int, default=20, help="timed runs per entry of the spaced report")
+    ap.add_argument("--host-reps", type=int, default=3, help="timed runs of the host route in the spaced report (0: leave it out)")
+    ap.add_argument("--report-out", default=None, help="also write the spaced report (with the run's header) to this file")
+    ap.add_argument("--report-only", action="store_true", help="skip the test_single_volume timings")
     args = ap.parse_args()
+    if args.spacing is not None:
+        SURFACE["spacing"] = tuple(args.spacing)
+    if args.nsd is not None:
+        SURFACE["nsd_tolerance"] = args.nsd
     dev = torch.device("cuda:0")
     kw = MODEL_CONFIGS["acdc"]["kw"]
     net = CENet(**kw)
@@ -186,10 +300,11 @@ def main():
     net = net.to(dev).eval()
     kern.set_compute_bf16(args.bf16)
     res = {"tool": "volume_infer", "device": torch.cuda.get_device_name(0), "kernel_src_sha16": build.source_sha16(),
-           "precision": "bf16" if args.bf16 else "fp32", "patch": list(PATCH), "batch_slices": 32, "unit": "ms", "metrics_method": args.metrics, "tta": args.tta, "volumes": {}}
+           "precision": "bf16" if args.bf16 else "fp32", "patch": list(PATCH), "batch_slices": 32, "unit": "ms", "metrics_method": args.metrics, "tta": args.tta,
+           "spacing": args.spacing, "nsd_tolerance": args.nsd, "volumes": {}}
     real_metric = evaluate.label_metrics
     for name, shape in VOLUMES.items():
-        if args.only and name != args.only:
+        if (args.only and name != args.only) or args.report_only:
             continue
         image, label = make_volume(shape, seed=sum(shape))
         # how much work the surface metrics would be on this prediction
@@ -198,9 +313,9 @@ def main():
         pairs = border_pairs(pred, lab_d, K)[0]
         timed_metrics = args.metrics != "pairs" or pairs <= args.metrics_cap
         if timed_metrics:
-            evaluate.label_metrics = lambda p, g, k, kind="acdc", method=args.metrics: real_metric(p, g, k, kind, method)
+            evaluate.label_metrics = lambda p, g, k, kind="acdc", method=args.metrics, **kw: real_metric(p, g, k, kind, method, **kw)
         else:
-            evaluate.label_metrics = lambda p, g, k, kind="acdc", method=None: [(0.0, 0.0, 0.0, 0.0)] * (k - 1)
+            evaluate.label_metrics = lambda p, g, k, kind="acdc", method=None, **kw: [(0.0,) * (5 if args.nsd else 4)] * (k - 1)
         entry = {"shape": list(shape), "max_border_pairs": pairs, "metrics_timed": timed_metrics}
         preds = {}
         for mode, tta in [("host", None), ("device", None)] + ([("device_tta", args.tta)] if args.tta else []):
@@ -218,7 +333,12 @@ def main():
         entry["class_dice"] = {m: [round(v, 6) for v in preds[m]] for m in preds}
         entry["class_dice_equal"] = preds["host"] == preds["device"]
         res["volumes"][name] = entry
-    if args.report:
+    if args.report and args.spacing is not None:
+        res["metrics_spacing"] = spaced_report(net, dev, args.only, tuple(args.spacing), args.nsd, args.reps, args.host_reps)
+        if args.report_out:
+            with open(args.report_out, "w") as f:
+                f.write(json.dumps({k: v for k, v in res.items() if k != "volumes"}) + "\n")
+    elif args.report:
         res["metrics"] = metrics_report(net, dev, args.metrics_cap, args.only)
     print(json.dumps(res))
 
