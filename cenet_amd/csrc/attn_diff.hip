@@ -8,8 +8,9 @@
 // Design (wave64, v_mfma_f32_32x32x16_bf16; C/D: lane = column, 16 registers = rows (r&3) + 8(r>>2) + 4(lane>>5)):
 //   * a wave owns 32-row tiles of the side that stays fixed (queries in fwd / dQ, keys in dK/dV) for BOTH softmax heads of
 //     a pair; the four waves of a workgroup share the streamed side: each 32-row tile is fetched once per workgroup with
-//     16-byte loads (register prefetch one tile ahead) into a double-buffered ROW-MAJOR bf16 image in LDS, one barrier per
-//     tile;
+//     16-byte loads (register prefetch one tile ahead: the loads of tile t + 1 are issued in front of the body of tile t and
+//     waited for behind it, tools/isa_loops.py shows the order per instance) into a double-buffered ROW-MAJOR bf16 image in
+//     LDS, one barrier per tile;
 //   * scores are computed transposed w.r.t. the fixed side (S^T = K Q^T in fwd / dQ, S = Q K^T in dK/dV), so the fixed index is
 //     the MFMA column = the lane: softmax state (max, sum, lse, delta) is one scalar per lane, a row reduction is 15 in-lane
 //     ops + one exchange with lane ^ 32, and the probability registers ARE the B operand of the next product (k-step s takes
@@ -70,6 +71,16 @@ __device__ __forceinline__ void da_wave_sync() {
 #endif
 }
 
+// every global load issued so far has landed (vmcnt(0); expcnt / lgkmcnt left alone).  Stands once between the prologue loads
+// (operand fragments, tile 0) and the key / query loop: the prologue's own wait sits inside the divergent block of its LDS write,
+// so without this the loop is entered with loads that MAY be pending and the compiler waits for them in front of the first
+// MFMA of every trip — behind the trip's prefetch.
+__device__ __forceinline__ void da_loads_landed() {
+#ifndef CENET_HOSTSIM_BUILD
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+#endif
+}
+
 struct DiffArgs {
   const bf *q, *k, *v;  // row-major: q, k [B, N, 2H*hd] ; v [B, N, H*2hd]
   bf* U;                // [B, 2H, N, 2hd]
@@ -83,18 +94,49 @@ struct DiffArgs {
 };
 
 // ---- LDS images -------------------------------------------------------------------------------------------------------------
+// one 16-byte chunk in registers (chunks are 16-byte aligned: da_fill checks the bases, every row and column offset is a multiple
+// of 8 elements).  A 4-word vector, not a byte copy into an unsigned[4]: with several chunks per thread the compiler took the
+// copied registers apart into 16-bit pieces and put them together again with shifts and masks (64 - 100 vector instructions per
+// trip in the dK/dV kernels at HDP >= 32).
+#ifdef CENET_HOSTSIM_BUILD
+struct da_u4 { unsigned x, y, z, w; };
+#else
+typedef unsigned da_u4 __attribute__((ext_vector_type(4)));
+#endif
 // One staged 16-byte chunk of a thread: 8 consecutive elements of one global row -> 8 consecutive elements of one image row.
+// A fetch is a straight line of loads: every thread loads 16 bytes for every chunk slot, unconditionally, from an address that
+// always lies inside the chunk's tensor — a row beyond the tensor reads the tensor's last row instead, a chunk in the zero
+// padding of the image (or a slot past the image) reads a real chunk of the same tensor.  What the image gets in those cases
+// (the fill pattern) is selected on the landed registers, in da_land, directly in front of the LDS write.  (A load under a
+// branch sits in a basic block of its own, followed by its wait: at HDP >= 32 the dK/dV kernels went through three to seven
+// memory round trips one after another at the top of every trip, before the first MFMA.)  For the same reason the loops
+// fetch on EVERY trip, the last one included (its rows are all clamped, nothing of it is staged): under `if (more)` the
+// prefetch registers are carried around the branch, the loads land in temporaries and are copied — behind a wait.
 struct DaChunk {
-  const bf* g;   // global address of the chunk in tile 0 (nullptr: the chunk lies in the zero padding of the image)
-  int lrow;      // row inside the 32-row tile
-  int loff;      // element offset inside the image
+  const bf* g;   // address of the chunk's columns in row 0 of its tensor (padding chunk / empty slot: of a real chunk)
+  int lrow;      // row inside the 32-row tile; DA_NOROW: padding chunk or empty slot (never a row of the tensor)
+  int loff;      // element offset inside the image (-1: empty slot, nothing is staged)
   unsigned fill; // low word of the 16-byte fill pattern for rows beyond the tensor (rest zero)
 };
-__device__ __forceinline__ void da_fetch(const DaChunk& c, long tile_step, int rows_left, unsigned (&r)[4]) {
-  r[0] = c.fill;
-  r[1] = r[2] = r[3] = 0u;
-  if (c.g && c.lrow < rows_left) memcpy(r, c.g + tile_step, 16);
-  else if (!c.g) r[0] = 0u;
+#define DA_NOROW 0x40000000
+// row0 = first row of the tile, N = rows of the tensor (>= 1), stride = elements per row
+__device__ __forceinline__ void da_fetch(const DaChunk& c, int row0, int N, int stride, da_u4& r) {
+  const int row = row0 + c.lrow < N ? row0 + c.lrow : N - 1;
+  r = *(const da_u4*)(c.g + (long)row * stride);
+}
+// the staged value of a fetched chunk: the landed bytes for a row of the tensor, the fill pattern otherwise; H4 (half = 0 / 1, -1:
+// not a q / k chunk): the two heads of a pair share the 16-byte row, the chunk keeps half `half` in its low 8 bytes (da_half)
+__device__ __forceinline__ da_u4 da_land(const DaChunk& c, int rows_left, da_u4 r, int half) {
+  const bool ok = c.lrow < rows_left;
+  r.x = ok ? r.x : c.fill;
+  r.y = ok ? r.y : 0u;
+  r.z = ok ? r.z : 0u;
+  r.w = ok ? r.w : 0u;
+  if (half >= 0) {
+    if (half) r.x = r.z, r.y = r.w;
+    r.z = r.w = 0u;
+  }
+  return r;
 }
 // row-major fragment: 8 consecutive columns [col + 8hh, +8) of image row `row`
 __device__ __forceinline__ bf16x8 da_rm(const bf* img, int pitch, int row, int col, int hh) {
@@ -219,35 +261,34 @@ __global__ __launch_bounds__(256, da_fwd_wg_per_cu(HDP, MINB, ONE)) void dattn_f
     ch[j].fill = 0u;
     hs[j] = -1;
     if (id >= NCH) {
-      ch[j].g = nullptr;
-      ch[j].lrow = 0;
+      ch[j].g = kb;
+      ch[j].lrow = DA_NOROW;
       ch[j].loff = -1;
     } else if (id < 32 * G::CK) {
       const int row = id / G::CK, cc = id - row * G::CK, s = cc / (HDP / 8), c8 = cc - s * (HDP / 8);
-      ch[j].lrow = row;
+      const bool real = H4 ? c8 == 0 : 8 * c8 < hd;  // (else: zero padding of the image, loads the head's first chunk)
+      ch[j].lrow = real ? row : DA_NOROW;
       ch[j].loff = row * G::KP + s * HDP + 8 * c8;
-      ch[j].g = H4 ? (c8 == 0 ? kb + (long)row * E + 2 * h * hd : nullptr)
-                   : (8 * c8 < hd ? kb + (long)row * E + (2 * h + s) * hd + 8 * c8 : nullptr);
+      ch[j].g = H4 ? kb + 2 * h * hd : kb + (2 * h + s) * hd + (real ? 8 * c8 : 0);
       hs[j] = s;
     } else {
       const int id2 = id - 32 * G::CK, row = id2 / G::CV, c8 = id2 - row * G::CV;
-      ch[j].lrow = row;
+      const bool real = 8 * c8 < dv;
+      ch[j].lrow = real ? row : DA_NOROW;
       ch[j].loff = KIMG + row * G::VPT + 8 * c8;
-      ch[j].g = 8 * c8 < dv ? vb + (long)row * (a.H * dv) + 8 * c8 : nullptr;
+      ch[j].g = vb + (real ? 8 * c8 : 0);
     }
   }
-  unsigned pre[CPT][4];
+  da_u4 pre[CPT];
+  // (k and v rows have the same length: E = 2 H hd = H dv elements)
   auto fetch = [&](int k0) __attribute__((always_inline)) {
 #pragma unroll
-    for (int j = 0; j < CPT; ++j) {
-      da_fetch(ch[j], (long)k0 * (ch[j].loff < KIMG ? E : a.H * dv), N - k0, pre[j]);
-      if (H4 && hs[j] >= 0) da_half(pre[j], hs[j]);
-    }
+    for (int j = 0; j < CPT; ++j) da_fetch(ch[j], k0, N, E, pre[j]);
   };
-  auto stage = [&](int buf) __attribute__((always_inline)) {
+  auto stage = [&](int buf, int k0) __attribute__((always_inline)) {  // k0: first key of the fetched tile
 #pragma unroll
     for (int j = 0; j < CPT; ++j)
-      if (ch[j].loff >= 0) memcpy(lds + buf * IMG + ch[j].loff, pre[j], 16);
+      if (ch[j].loff >= 0) *(da_u4*)(lds + buf * IMG + ch[j].loff) = da_land(ch[j], N - k0, pre[j], H4 ? hs[j] : -1);
   };
 
   bf16x8 qf[QT][2][NKS];
@@ -341,15 +382,16 @@ __global__ __launch_bounds__(256, da_fwd_wg_per_cu(HDP, MINB, ONE)) void dattn_f
   };
   const int nfull = N & ~31;  // keys in full tiles; the same for every wave: equal barrier counts whatever q0
   fetch(0);
-  stage(0);
+  stage(0, 0);
+  da_loads_landed();
   __syncthreads();
   int cur = 0;
   for (int k0 = 0; k0 < nfull; k0 += 32) {
     const bool more = k0 + 32 < N;  // (the ragged tile is fetched and staged like any other)
-    if (more) fetch(k0 + 32);
+    fetch(k0 + 32);
     // (wave-uniform: a wave past the last query only helps with the staging)
     if (q0 < N) tile(da_false(), lds + cur * IMG, lds + cur * IMG + KIMG, 32);
-    if (more) stage(cur ^ 1);
+    if (more) stage(cur ^ 1, k0 + 32);
     __syncthreads();
     cur ^= 1;
   }
@@ -418,35 +460,34 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : (HDP <= 16 ? 3 : 2)) void dattn
     ch[j].fill = 0u;
     hs[j] = -1;
     if (id >= NCH) {
-      ch[j].g = nullptr;
-      ch[j].lrow = 0;
+      ch[j].g = kb;
+      ch[j].lrow = DA_NOROW;
       ch[j].loff = -1;
     } else if (id < 32 * G::CK) {
       const int row = id / G::CK, cc = id - row * G::CK, s = cc / (HDP / 8), c8 = cc - s * (HDP / 8);
-      ch[j].lrow = row;
+      const bool real = H4 ? c8 == 0 : 8 * c8 < hd;  // (else: zero padding of the image, loads the head's first chunk)
+      ch[j].lrow = real ? row : DA_NOROW;
       ch[j].loff = row * G::KP + s * HDP + 8 * c8;
-      ch[j].g = H4 ? (c8 == 0 ? kb + (long)row * E + 2 * h * hd : nullptr)
-                   : (8 * c8 < hd ? kb + (long)row * E + (2 * h + s) * hd + 8 * c8 : nullptr);
+      ch[j].g = H4 ? kb + 2 * h * hd : kb + (2 * h + s) * hd + (real ? 8 * c8 : 0);
       hs[j] = s;
     } else {
       const int id2 = id - 32 * G::CK, row = id2 / G::CV, c8 = id2 - row * G::CV;
-      ch[j].lrow = row;
+      const bool real = 8 * c8 < dv;
+      ch[j].lrow = real ? row : DA_NOROW;
       ch[j].loff = KIMG + row * G::VPR + 8 * c8;
-      ch[j].g = 8 * c8 < dv ? vb + (long)row * (a.H * dv) + 8 * c8 : nullptr;
+      ch[j].g = vb + (real ? 8 * c8 : 0);
     }
   }
-  unsigned pre[CPT][4];
+  da_u4 pre[CPT];
+  // (k and v rows have the same length: E = 2 H hd = H dv elements)
   auto fetch = [&](int k0) __attribute__((always_inline)) {
 #pragma unroll
-    for (int j = 0; j < CPT; ++j) {
-      da_fetch(ch[j], (long)k0 * (ch[j].loff < KIMG ? E : a.H * dv), N - k0, pre[j]);
-      if (H4 && hs[j] >= 0) da_half(pre[j], hs[j]);
-    }
+    for (int j = 0; j < CPT; ++j) da_fetch(ch[j], k0, N, E, pre[j]);
   };
-  auto stage = [&](int buf) __attribute__((always_inline)) {
+  auto stage = [&](int buf, int k0) __attribute__((always_inline)) {  // k0: first key of the fetched tile
 #pragma unroll
     for (int j = 0; j < CPT; ++j)
-      if (ch[j].loff >= 0) memcpy(lds + buf * IMG + ch[j].loff, pre[j], 16);
+      if (ch[j].loff >= 0) *(da_u4*)(lds + buf * IMG + ch[j].loff) = da_land(ch[j], N - k0, pre[j], H4 ? hs[j] : -1);
   };
 
   bf16x8 qf[2][NKS], gf[NH][NKD];
@@ -528,14 +569,15 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : (HDP <= 16 ? 3 : 2)) void dattn
   };
   const int nfull = N & ~31;
   fetch(0);
-  stage(0);
+  stage(0, 0);
+  da_loads_landed();
   __syncthreads();
   int cur = 0;
   for (int k0 = 0; k0 < nfull; k0 += 32) {
     const bool more = k0 + 32 < N;
-    if (more) fetch(k0 + 32);
+    fetch(k0 + 32);
     if (q0 < N) tile(da_false(), lds + cur * IMG, lds + cur * IMG + KIMG, 32);
-    if (more) stage(cur ^ 1);
+    if (more) stage(cur ^ 1, k0 + 32);
     __syncthreads();
     cur ^= 1;
   }
@@ -585,54 +627,52 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : 2) void dattn_bwd_dkv_kernel(Di
   const int ki = k0 + r < N ? k0 + r : N - 1;
 
   DaChunk ch[CPT];
-  long gstep[CPT];  // elements per 32-row tile step of the chunk's tensor
+  int gstride[CPT];  // elements per row of the chunk's tensor
   int hs[CPT];      // H4: which half of the staged 16-byte pair row the chunk keeps (-1: not a q chunk)
 #pragma unroll
   for (int j = 0; j < CPT; ++j) {
     int id = tid + 256 * j;
     ch[j].fill = 0u;
     hs[j] = -1;
-    gstep[j] = 0;
     if (id >= NCH) {
-      ch[j].g = nullptr;
-      ch[j].lrow = 0;
+      ch[j].g = qb;
+      ch[j].lrow = DA_NOROW;
       ch[j].loff = -1;
+      gstride[j] = E;
     } else if (id < 32 * G::CK) {  // Q rows, both heads
       const int row = id / G::CK, cc = id - row * G::CK, s = cc / (HDP / 8), c8 = cc - s * (HDP / 8);
-      ch[j].lrow = row;
+      const bool real = H4 ? c8 == 0 : 8 * c8 < hd;  // (else: zero padding of the image, loads the head's first chunk)
+      ch[j].lrow = real ? row : DA_NOROW;
       ch[j].loff = row * G::KP + s * HDP + 8 * c8;
-      ch[j].g = H4 ? (c8 == 0 ? qb + (long)row * E + 2 * h * hd : nullptr)
-                   : (8 * c8 < hd ? qb + (long)row * E + (2 * h + s) * hd + 8 * c8 : nullptr);
+      ch[j].g = H4 ? qb + 2 * h * hd : qb + (2 * h + s) * hd + (real ? 8 * c8 : 0);
       hs[j] = s;
-      gstep[j] = 32L * E;
+      gstride[j] = E;
     } else if ((id -= 32 * G::CK) < NH * 32 * G::CV) {  // dU rows of head s
       const int s = id / (32 * G::CV), id2 = id - s * 32 * G::CV, row = id2 / G::CV, c8 = id2 - row * G::CV;
-      ch[j].lrow = row;
+      const bool real = 8 * c8 < dv;
+      ch[j].lrow = real ? row : DA_NOROW;
       ch[j].loff = QIMG + s * GIMG + row * G::VPR + 8 * c8;
-      ch[j].g = 8 * c8 < dv ? a.dU + (hb0 + (long)s * N + row) * dv + 8 * c8 : nullptr;
-      gstep[j] = 32L * dv;
+      ch[j].g = a.dU + (hb0 + (long)s * N) * dv + (real ? 8 * c8 : 0);
+      gstride[j] = dv;
     } else {  // statistics rows: chunk (row, s, kind): kind 0 = lse / scale, 1 = delta
       id -= NH * 32 * G::CV;
       const int row = id / (2 * NH), s = (id - row * 2 * NH) >> 1, kind = id & 1;
       ch[j].lrow = row;
       ch[j].loff = QIMG + NH * GIMG + row * AP + s * 16 + 8 * kind;
-      ch[j].g = a.aug + (hb0 + (long)s * N + row) * 16 + 8 * kind;
+      ch[j].g = a.aug + (hb0 + (long)s * N) * 16 + 8 * kind;
       ch[j].fill = kind == 0 ? 0x7149u : 0u;  // rows beyond N: lse / scale = 1e30 -> probability 0
-      gstep[j] = 32L * 16;
+      gstride[j] = 16;
     }
   }
-  unsigned pre[CPT][4];
+  da_u4 pre[CPT];
   auto fetch = [&](int q0) __attribute__((always_inline)) {
 #pragma unroll
-    for (int j = 0; j < CPT; ++j) {
-      da_fetch(ch[j], (q0 >> 5) * gstep[j], N - q0, pre[j]);
-      if (H4 && hs[j] >= 0) da_half(pre[j], hs[j]);
-    }
+    for (int j = 0; j < CPT; ++j) da_fetch(ch[j], q0, N, gstride[j], pre[j]);
   };
-  auto stage = [&](int buf) __attribute__((always_inline)) {
+  auto stage = [&](int buf, int q0) __attribute__((always_inline)) {  // q0: first query of the fetched tile
 #pragma unroll
     for (int j = 0; j < CPT; ++j)
-      if (ch[j].loff >= 0) memcpy(lds + buf * IMG + ch[j].loff, pre[j], 16);
+      if (ch[j].loff >= 0) *(da_u4*)(lds + buf * IMG + ch[j].loff) = da_land(ch[j], N - q0, pre[j], H4 ? hs[j] : -1);
   };
 
   bf16x8 kfB[2][NKS], vfB[NKD];
@@ -656,12 +696,13 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : 2) void dattn_bwd_dkv_kernel(Di
   for (int dt = 0; dt < NDT; ++dt) dV[dt] = da_zero();
 
   fetch(0);
-  stage(0);
+  stage(0, 0);
+  da_loads_landed();
   __syncthreads();
   int cur = 0;
   for (int q0 = 0; q0 < N; q0 += 32) {
     const bool more = q0 + 32 < N;
-    if (more) fetch(q0 + 32);
+    fetch(q0 + 32);
     const bf* Qimg = lds + cur * IMG;
     const bf* Aimg = Qimg + QIMG + NH * GIMG;
     if (k0 < N) {
@@ -707,7 +748,7 @@ __global__ __launch_bounds__(256, HDP > 32 ? 1 : 2) void dattn_bwd_dkv_kernel(Di
         }
       }
     }
-    if (more) stage(cur ^ 1);
+    if (more) stage(cur ^ 1, q0 + 32);
     __syncthreads();
     cur ^= 1;
   }
