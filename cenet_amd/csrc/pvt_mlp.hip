@@ -747,19 +747,58 @@ __global__ __launch_bounds__(256) void pvt_mlp_lnfold_kernel(const float* __rest
   }
 }
 
-static bool pvt_mlp_geo(int H, int W, int& TH, int& TW) {
-  if (W % 14 != 0) return false;
-  TW = 14;
-  if (H % 8 == 0) TH = 8;
-  else if (H % 7 == 0) TH = 7;
+// The launch geometry of all three kernels, decided in ONE place (cenet_pvt_mlp_bwd_plan exports it).
+struct PvtMlpPlan {
+  int TH, TW, tiles_x, tiles_per_img;  // forward and K2: workgroup = tile
+  int k1th, k1_tiles_per_img, k1_tpw, k1_runs;  // K1: workgroup = (slab, run of k1_tpw tiles of k1th rows, image)
+};
+// the exact tiling of an H x W map, or false where there is none
+static bool pvt_mlp_geo(int H, int W, PvtMlpPlan& p) {
+  if (H <= 0 || W <= 0 || W % 14 != 0) return false;
+  p.TW = 14;
+  if (H % 8 == 0) p.TH = 8;
+  else if (H % 7 == 0) p.TH = 7;
   else return false;
+  p.tiles_x = W / p.TW;
+  p.tiles_per_img = p.tiles_x * (H / p.TH);
   return true;
 }
 
 /* 1 when (C, HD, H, W) has a fused instance */
 extern "C" int cenet_pvt_mlp_supported(int C, int HD, int H, int W) {
-  int TH, TW;
-  return (C == 64 || C == 128) && HD % 64 == 0 && HD >= 64 && pvt_mlp_geo(H, W, TH, TW) ? 1 : 0;
+  PvtMlpPlan p;
+  return (C == 64 || C == 128) && HD % 64 == 0 && HD >= 64 && pvt_mlp_geo(H, W, p) ? 1 : 0;
+}
+
+static int pvt_mlp_plan(int B, int H, int W, int C, int HD, PvtMlpPlan& p) {
+  if (B <= 0) return CENET_EINVAL;
+  if (!cenet_pvt_mlp_supported(C, HD, H, W) || !pvt_mlp_geo(H, W, p)) return CENET_EUNSUPPORTED;
+  // K1 and K2 meet only through gu [B, N, HD] (token-indexed) and are tiled INDEPENDENTLY: K2 (workgroup = tile, the LayerNorm
+  // partials in ws are per K2 tile) keeps the forward's tile; K1 (workgroup = slab x run of tiles x image) takes 4-row tiles where
+  // they divide the map — more, shorter runs: 94 -> 75 us at 28 x 28 (the forward kernel with 4-row tiles is SLOWER: 90 -> 116 us,
+  // its depthwise phase then fills half the threads)
+  p.k1th = p.TH == 7 && H % 4 == 0 ? 4 : p.TH;  // (at 56 x 56 the 8-row tile wins: 97 vs 126 us)
+  p.k1_tiles_per_img = p.tiles_x * (H / p.k1th);
+  // runs of tiles per (slab, image): as few as still give ~1 024 workgroups (two rounds at two per CU) — a run keeps the W2 slab,
+  // the depthwise weights and the weight-gradient accumulators of its slab; 4 / 2 tiles per run measured 0.04 ms slower than 7 / 7
+  int runs = 1024 / ((HD / 64) * B);
+  if (runs < 1) runs = 1;
+  p.k1_tpw = cdiv(p.k1_tiles_per_img, runs);
+  p.k1_runs = cdiv(p.k1_tiles_per_img, p.k1_tpw);
+  return CENET_OK;
+}
+
+/* the tiling cenet_pvt_mlp_fwd_bf16 / cenet_pvt_mlp_bwd_bf16 launch with (any output pointer may be NULL) */
+extern "C" int cenet_pvt_mlp_bwd_plan(int B, int H, int W, int C, int HD, int* tile_rows, int* k1_tile_rows,
+                                      int* k1_tiles_per_run, int* k1_runs) {
+  PvtMlpPlan p;
+  const int rc = pvt_mlp_plan(B, H, W, C, HD, p);
+  if (rc != CENET_OK) return rc;
+  if (tile_rows) *tile_rows = p.TH;
+  if (k1_tile_rows) *k1_tile_rows = p.k1th;
+  if (k1_tiles_per_run) *k1_tiles_per_run = p.k1_tpw;
+  if (k1_runs) *k1_runs = p.k1_runs;
+  return CENET_OK;
 }
 
 extern "C" int cenet_pvt_mlp_fwd_bf16(const bf16_t* x, const float* ln_g, const float* ln_b, float eps, const bf16_t* w1,
@@ -770,8 +809,9 @@ extern "C" int cenet_pvt_mlp_fwd_bf16(const bf16_t* x, const float* ln_g, const 
   const int nsave = (xn_out != nullptr) + (mean_out != nullptr) + (rstd_out != nullptr) + (h_out != nullptr) + (a_out != nullptr);
   if (nsave != 0 && nsave != 5) return CENET_EINVAL;  // all of the saved tensors or none
   if ((((uintptr_t)xn_out | (uintptr_t)h_out | (uintptr_t)a_out) & 15) != 0) return CENET_EUNSUPPORTED;
-  int TH, TW;
-  if (!cenet_pvt_mlp_supported(C, HD, H, W) || !pvt_mlp_geo(H, W, TH, TW)) return CENET_EUNSUPPORTED;
+  PvtMlpPlan pl;
+  if (const int rc = pvt_mlp_plan(B, H, W, C, HD, pl)) return rc;
+  const int TH = pl.TH;
   if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)ln_g | (uintptr_t)ln_b | (uintptr_t)b1 |
         (uintptr_t)b2) & 15) != 0 || (((uintptr_t)wd | (uintptr_t)bd) & 7) != 0)
     return CENET_EUNSUPPORTED;
@@ -779,8 +819,8 @@ extern "C" int cenet_pvt_mlp_fwd_bf16(const bf16_t* x, const float* ln_g, const 
   a.x = x; a.ln_g = ln_g; a.ln_b = ln_b; a.w1 = w1; a.b1 = b1; a.wd = wd; a.bd = bd; a.w2 = w2; a.b2 = b2; a.bscale = bscale;
   a.y = y; a.xn_out = xn_out; a.mean_out = mean_out; a.rstd_out = rstd_out; a.h_out = h_out; a.a_out = a_out;
   a.H = H; a.W = W; a.HD = HD; a.eps = eps;
-  a.tiles_x = W / TW;
-  a.tiles_per_img = a.tiles_x * (H / TH);
+  a.tiles_x = pl.tiles_x;
+  a.tiles_per_img = pl.tiles_per_img;
   const dim3 grid(B * a.tiles_per_img);
 #define PVT_FWD_GO(C_, TH_)                                                                  \
   if (C == C_ && TH == TH_) {                                                                 \
@@ -799,9 +839,9 @@ extern "C" int cenet_pvt_mlp_fwd_bf16(const bf16_t* x, const float* ln_g, const 
 
 /* floats of workspace cenet_pvt_mlp_bwd_bf16 needs */
 extern "C" long cenet_pvt_mlp_bwd_ws_floats(int B, int H, int W, int C) {
-  int TH, TW;
-  if (!pvt_mlp_geo(H, W, TH, TW)) return 0;
-  return (long)B * (W / TW) * (H / TH) * 3 * C;
+  PvtMlpPlan pl;
+  if (!pvt_mlp_geo(H, W, pl)) return 0;
+  return (long)B * pl.tiles_per_img * 3 * C;
 }
 
 /* backward of cenet_pvt_mlp_fwd_bf16 from its saved tensors, two launches (+ a fold of the LayerNorm affine gradients):
@@ -815,10 +855,12 @@ extern "C" int cenet_pvt_mlp_bwd_bf16(const bf16_t* g, const float* bscale, cons
                                       float* dwd_acc, float* dbd_acc, float* dln_g_acc, float* dln_b_acc, float* db2_acc,
                                       float* ws, int B, int H, int W, int C, int HD, hipStream_t stream) {
   if (!g || !w1 || !w2 || !wd || !bd || !h || !x || !ln_g || !mean || !rstd || !gu || !dh || !dx || !dwd_acc || !dbd_acc ||
-      !dln_g_acc || !dln_b_acc || !ws || B <= 0 || (up_scale != nullptr) != (dxs != nullptr))
+      !dln_g_acc || !dln_b_acc || B <= 0 || (up_scale != nullptr) != (dxs != nullptr))
     return CENET_EINVAL;
-  int TH, TW;
-  if (!cenet_pvt_mlp_supported(C, HD, H, W) || !pvt_mlp_geo(H, W, TH, TW)) return CENET_EUNSUPPORTED;
+  PvtMlpPlan pl;
+  if (const int rc = pvt_mlp_plan(B, H, W, C, HD, pl)) return rc;
+  if (!ws) return CENET_EINVAL;  // (after the shape: cenet_pvt_mlp_bwd_ws_floats is 0 for a map without a tiling)
+  const int TH = pl.TH, k1th = pl.k1th;
   if ((((uintptr_t)g | (uintptr_t)h | (uintptr_t)x | (uintptr_t)gu | (uintptr_t)dh | (uintptr_t)dx | (uintptr_t)dxs |
         (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)ln_g) & 15) != 0 || (((uintptr_t)wd | (uintptr_t)bd) & 7) != 0)
     return CENET_EUNSUPPORTED;
@@ -827,24 +869,12 @@ extern "C" int cenet_pvt_mlp_bwd_bf16(const bf16_t* g, const float* bscale, cons
   a.dwd = dwd_acc; a.dbd = dbd_acc; a.x = x; a.ln_g = ln_g; a.mean = mean; a.rstd = rstd; a.dx = dx; a.ws = ws;
   a.up_scale = up_scale; a.dxs = dxs;
   a.H = H; a.W = W; a.HD = HD;
-  a.tiles_x = W / TW;
-  a.tiles_per_img = a.tiles_x * (H / TH);
-  a.tpw = a.tiles_per_img >= 16 ? 4 : 2;
-  if (a.tpw > a.tiles_per_img) a.tpw = a.tiles_per_img;
-  // K1 and K2 meet only through gu [B, N, HD] (token-indexed) and are tiled INDEPENDENTLY: K2 (workgroup = tile, the LayerNorm
-  // partials in ws are per K2 tile) keeps the forward's tile; K1 (workgroup = slab x run of tiles x image) takes 4-row tiles where
-  // they divide the map — more, shorter runs: 94 -> 75 us at 28 x 28 (the forward kernel with 4-row tiles is SLOWER: 90 -> 116 us,
-  // its depthwise phase then fills half the threads)
-  const int k1th = TH == 7 && H % 4 == 0 ? 4 : TH;  // (at 56 x 56 the 8-row tile wins: 97 vs 126 us)
-  PvtBwdArgs a1 = a;
-  a1.tiles_per_img = a.tiles_x * (H / k1th);
-  {  // runs of tiles per (slab, image): as few as still give ~1 024 workgroups (two rounds at two per CU) — a run keeps the W2 slab,
-     // the depthwise weights and the weight-gradient accumulators of its slab; 4 / 2 tiles per run measured 0.04 ms slower than 7 / 7
-    int runs = 1024 / ((HD / 64) * B);
-    if (runs < 1) runs = 1;
-    a1.tpw = cdiv(a1.tiles_per_img, runs);
-  }
-  const dim3 g1(HD / 64, cdiv(a1.tiles_per_img, a1.tpw), B), g2(B * a.tiles_per_img);
+  a.tiles_x = pl.tiles_x;
+  a.tiles_per_img = pl.tiles_per_img;
+  PvtBwdArgs a1 = a;  // K1's own tiling (pvt_mlp_plan)
+  a1.tiles_per_img = pl.k1_tiles_per_img;
+  a1.tpw = pl.k1_tpw;
+  const dim3 g1(HD / 64, pl.k1_runs, B), g2(B * a.tiles_per_img);
   if (g1.y > 65535 || g1.z > 65535) return CENET_EUNSUPPORTED;
 #define PVT_BWD_GO(C_, TH_)                                                                              \
   if (C == C_ && TH == TH_) {                                                                             \

@@ -674,6 +674,14 @@ def pvt_mlp_bwd(g, bscale, w1, w2, wd, bd, h, x, ln_g, mean, rstd, gu, dh, dx, d
           dln_b, db2, ws, B, H, W, Cn, HD)
 
 
+def pvt_mlp_bwd_plan(B, H, W, Cn, HD):
+    """the tiling pvt_mlp_fwd / pvt_mlp_bwd launch with -> (tile_rows, k1_tile_rows, k1_tiles_per_run, k1_runs), see
+    cenet_pvt_mlp_bwd_plan in include/cenet_hip.h (host only; raises where there is no fused instance)"""
+    out = [C.c_int(0) for _ in range(4)]
+    _lib.check(_lib.lib().cenet_pvt_mlp_bwd_plan(B, H, W, Cn, HD, *(C.addressof(o) for o in out)), "cenet_pvt_mlp_bwd_plan")
+    return tuple(o.value for o in out)
+
+
 def dw_wgrad_nchw(x, sxb, dy, sgb, dw, dbias, B, Cn, H, W, dil, x_off=0, g_off=0):
     _call("cenet_dwconv3x3_wgrad_nchw_acc_f32", Ptr(x, x_off), sxb, Ptr(dy, g_off), sgb, dw, dbias, B, Cn, H, W, dil)
 

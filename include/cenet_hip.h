@@ -358,8 +358,20 @@ int cenet_pvt_mlp_fwd_bf16(const unsigned short* x, const float* ln_g, const flo
  * fc1's output (operand of the fc1 weight gradient dW1 = dh^T xn; the fc2 weight gradient is dW2 = g^T a with the forward's saved a,
  * which already carries s_b); dx = g + LayerNormBackward(dh . W1); dwd / dbd / dln_g / dln_b and db2 (fc2 bias gradient =
  * column sums of s_b g; may be NULL) are ADDED into.
+ * Where the backward rounds: gu = bf16(da * GELU'(DW3x3(h) + bd)) with da = bf16(s_b (g . W2)) — the product with W2 is rounded to
+ * bf16 once (s_b applied in fp32 before that rounding) BEFORE the multiply by GELU'.  dwd / dbd accumulate the fp32 product
+ * da * GELU' (against the h windows; dbd: its plain sum) BEFORE gu is rounded to bf16, in fp32 and in no fixed order.  dh and dx
+ * are computed from gu and dh AS STORED.  GELU' is the bf16 form stated at cenet_dwact_* (the forward's GELU likewise).
+ * With up_scale [B] and dxs (both or neither: CENET_EINVAL otherwise), dxs = bf16(up_scale_b * float(dx as stored)).
  * ws: cenet_pvt_mlp_bwd_ws_floats(B, H, W, C) floats. */
 long cenet_pvt_mlp_bwd_ws_floats(int B, int H, int W, int C);
+/* The tiling both entry points launch with, for tests that pin which code path a shape takes: tile_rows = rows of the 14-column
+ * token tile of the forward kernel and of the second backward kernel (dh, dx); k1_tile_rows = rows of the first backward kernel's
+ * (gu, dwd, dbd) tile; a workgroup of that kernel walks a run of at most k1_tiles_per_run consecutive tiles of one image and one
+ * 64-channel slab, k1_runs runs per image (the last one may be shorter).  Any output pointer may be NULL.  Host only, nothing is
+ * launched.  CENET_EUNSUPPORTED where cenet_pvt_mlp_supported(C, HD, H, W) is 0, CENET_EINVAL for B <= 0. */
+int cenet_pvt_mlp_bwd_plan(int B, int H, int W, int C, int HD, int* tile_rows, int* k1_tile_rows, int* k1_tiles_per_run,
+                           int* k1_runs);
 int cenet_pvt_mlp_bwd_bf16(const unsigned short* g, const float* bscale, const unsigned short* w1, const unsigned short* w2,
                            const float* wd, const float* bd, const unsigned short* h, const unsigned short* x, const float* ln_g,
                            const float* mean, const float* rstd, unsigned short* gu, unsigned short* dh, unsigned short* dx,
