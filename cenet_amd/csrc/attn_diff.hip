@@ -933,6 +933,59 @@ struct SraArgs {
   float scale;
 };
 
+// K and V of a (batch, head) into their resident images: NKB * 64 rows x 8 chunks each, rows >= Nk zero.  One fetch in the sense
+// of da_fetch / da_land: a thread owns 4 NKB chunk slots, loads them all back to back (a row >= Nk reads row Nk - 1 of the same
+// tensor), and the zero fill is selected on the landed registers in front of the LDS writes — one memory round trip, not one
+// per slot.  16 slots (NKB = 4) go as two batches of 8: 32 registers of chunks in flight beside the 49 of tile 0's rows, in an
+// instance that runs two waves per SIMD.
+template <int NKB, int KP>
+__device__ __forceinline__ void sra_stage_kv(const bf* kb, const bf* vb, int Nk, int C, bf* KVimg, int tid) {
+  constexpr int CPT = 4 * NKB, BATCH = CPT < 8 ? CPT : 8;
+#pragma unroll
+  for (int j0 = 0; j0 < CPT; j0 += BATCH) {
+    DaChunk ch[BATCH];
+    da_u4 pre[BATCH];
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      const int id = tid + 256 * (j0 + j), which = id / (NKB * 512), rem = id - which * (NKB * 512), row = rem >> 3, c8 = rem & 7;
+      ch[j].g = (which ? vb : kb) + 8 * c8;
+      ch[j].lrow = row;
+      ch[j].loff = which * (NKB * 64 * KP) + row * KP + 8 * c8;  // (KVimg: the K image, the V image right behind it)
+      ch[j].fill = 0u;
+      da_fetch(ch[j], 0, Nk, 2 * C, pre[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) *(da_u4*)(KVimg + ch[j].loff) = da_land(ch[j], Nk, pre[j], -1);
+  }
+}
+
+// One 32-query tile of a lane in registers: 64 features of q, dO and o as 4 chunks each (k-step ks: columns 16 ks + 8 hh) and the
+// row's lse.  sra_fetch is a straight line of 13 loads from row qi (clamped by the caller: always a row of the tensor).
+struct SraTile {
+  da_u4 q[4], g[4], u[4];
+  float lse;
+};
+__device__ __forceinline__ void sra_fetch(SraTile& x, const bf* qb, const bf* gb, const bf* ob, const float* lse, int qi, int C,
+                                          int hh) {
+  const long off = (long)qi * C + 8 * hh;
+  x.lse = lse[qi];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    x.q[ks] = *(const da_u4*)(qb + off + 16 * ks);
+    x.g[ks] = *(const da_u4*)(gb + off + 16 * ks);
+    x.u[ks] = *(const da_u4*)(ob + off + 16 * ks);
+  }
+}
+__device__ __forceinline__ void sra_fetch_q(da_u4 (&x)[4], const bf* qb, int qi, int C, int hh) {
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) x[ks] = *(const da_u4*)(qb + (long)qi * C + 8 * hh + 16 * ks);
+}
+__device__ __forceinline__ bf16x8 da_frag(const da_u4& r) {
+  bf16x8 f;
+  memcpy(&f, &r, 16);
+  return f;
+}
+
 // NKB = 64-key blocks resident in LDS; DQ / DKV = which gradients this instance produces:
 //   <1, true, true>   the whole backward of a (batch, head) with <= 64 keys (the 224x224 presets: 49 keys);
 //   <4, true, false>  dQ over up to 256 resident keys (512x512 inputs: 256 keys under 4 096 .. 16 384 queries);
@@ -943,8 +996,12 @@ __global__ __launch_bounds__(256, DKV ? 1 : 2) void sra_bwd_kernel(SraArgs a) {
   constexpr int KP = 72, AP = 40;                     // image pitches (elements)
   constexpr int KVIMG = NKB * 64 * KP, QIMG = 32 * KP + 64, AIMG = 32 * AP;
   constexpr int WIMG = 2 * QIMG + AIMG;               // per-wave: Q image, dO image, statistics image
-  constexpr int LDS_EL = (DQ ? 2 * KVIMG : 0) + (DKV ? 4 * WIMG : 0);
-  static_assert(!DKV || LDS_EL * 2 >= 64 * 128 * 4, "the dK/dV reduction block reuses the images");
+  constexpr int IMG_EL = (DQ ? 2 * KVIMG : 0) + (DKV ? 4 * WIMG : 0);
+  // the dK/dV reduction reuses the images: four 128 x 64 fp32 blocks side by side, one per wave, rows pitched by RP floats (one
+  // workgroup per CU owns the CU's 160 KB)
+  constexpr int RP = 65, RED = 128 * RP;
+  constexpr int LDS_EL = DKV && 4 * RED * 2 > IMG_EL ? 4 * RED * 2 : IMG_EL;
+  static_assert(LDS_EL * 2 <= 160 * 1024, "one CU's LDS");
   static_assert(NKB == 1 || !DKV, "dK / dV accumulators exist for one 64-key block");
   __shared__ __attribute__((aligned(16))) bf lds[LDS_EL];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
@@ -964,18 +1021,17 @@ __global__ __launch_bounds__(256, DKV ? 1 : 2) void sra_bwd_kernel(SraArgs a) {
   bf* Qimg = lds + (DQ ? 2 * KVIMG : 0) + wave * WIMG;
   bf* Gimg = Qimg + QIMG;
   bf* Aimg = Gimg + QIMG;
-  if (DQ) {
-    // K and V of this (batch, head): NKB * 64 rows x 8 chunks each, rows >= Nk zero
-    for (int id = tid; id < 2 * NKB * 64 * 8; id += 256) {
-      const int which = id / (NKB * 512), rem = id - which * (NKB * 512), row = rem >> 3, c8 = rem & 7;
-      unsigned v4[4] = {0u, 0u, 0u, 0u};
-      if (row < Nk) memcpy(v4, (which ? vb : kb) + (long)row * 2 * C + 8 * c8, 16);
-      memcpy((which ? Vimg : Kimg) + row * KP + 8 * c8, v4, 16);
-    }
-  }
-  // B fragments of K^T / V^T for phase B: key = 32 kt + r
+  const float* lb = a.lse + ((long)b * a.H + h) * Nq;
+  const int q00 = (bid.x * 4 + wave) * 32 * a.tiles;
+  // tile 0's rows go first: they land with the K / V chunks behind them
+  SraTile nx;
+  sra_fetch(nx, qb, gb, ob, lb, q00 + r < Nq ? q00 + r : Nq - 1, C, hh);
+  if (DQ) sra_stage_kv<NKB, KP>(kb, vb, Nk, C, Kimg, tid);
+  // B fragments of K^T / V^T for phase B: key = 32 kt + r.  With DQ they are the rows of the resident images (da_rm(Kimg / Vimg,
+  // KP, 32 kt + r, 16 ks, hh): the same 16 bytes, rows >= Nk zero there as well) and phase B reads them from LDS per tile —
+  // their 64 registers hold the next tile's rows instead.  The dK/dV-only instance has no images and keeps them in registers.
   bf16x8 kfB[2][4], vfB[2][4];
-  if (DKV) {
+  if (DKV && !DQ) {
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -993,21 +1049,21 @@ __global__ __launch_bounds__(256, DKV ? 1 : 2) void sra_bwd_kernel(SraArgs a) {
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt) dK[kt][dt] = dV[kt][dt] = da_zero();
   __syncthreads();
+  da_loads_landed();
 
-  const int q00 = (bid.x * 4 + wave) * 32 * a.tiles;
   for (int t = 0; t < a.tiles; ++t) {
     const int q0 = q00 + 32 * t;
     if (q0 >= Nq) break;  // (wave-uniform)
     const int qi = q0 + r < Nq ? q0 + r : Nq - 1;
     const bool qok = q0 + r < Nq;
-    // ---- this tile's rows: B fragments for phase A, images for phase B ----
+    // ---- this tile's rows (fetched one trip ahead): B fragments for phase A, images for phase B ----
     bf16x8 qf[4], gf[4];
     float acc = 0.f;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      qf[ks] = da_ld8(qb + (long)qi * C + 16 * ks + 8 * hh, true);
-      gf[ks] = da_ld8(gb + (long)qi * C + 16 * ks + 8 * hh, true);
-      const bf16x8 uf = da_ld8(ob + (long)qi * C + 16 * ks + 8 * hh, true);
+      qf[ks] = da_frag(nx.q[ks]);
+      gf[ks] = da_frag(nx.g[ks]);
+      const bf16x8 uf = da_frag(nx.u[ks]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc += cenet_bf2f((unsigned short)gf[ks][j]) * cenet_bf2f((unsigned short)uf[j]);
       if (DKV) {
@@ -1019,8 +1075,11 @@ __global__ __launch_bounds__(256, DKV ? 1 : 2) void sra_bwd_kernel(SraArgs a) {
     }
     acc += __shfl_xor(acc, 32);
     const float delta = acc;
-    const float lse = a.lse[((long)b * a.H + h) * Nq + qi];
+    const float lse = nx.lse;
     const float lse2 = lse * DA_LOG2E;
+    // the next tile's rows, in flight across this tile's body.  Every trip fetches, the last one included (its rows are clamped
+    // and nothing of it is used): under `if (more)` the registers would be carried around the branch and land behind a wait.
+    sra_fetch(nx, qb, gb, ob, lb, q0 + 32 + r < Nq ? q0 + 32 + r : Nq - 1, C, hh);
     if (DKV) {  // statistics rows: lane half 0 writes lse / scale, half 1 writes delta (rows beyond Nq: lse / scale = 1e30 -> P = 0)
       unsigned short row8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       da_split3(hh == 0 ? (qok ? lse / a.scale : 1.0e30f) : (qok ? delta : 0.f), row8);
@@ -1078,8 +1137,8 @@ __global__ __launch_bounds__(256, DKV ? 1 : 2) void sra_bwd_kernel(SraArgs a) {
       f32x16 S = da_zero(), dP = da_zero();
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        S = DA_MFMA(da_rm(Qimg, KP, r, 16 * ks, hh), kfB[kt][ks], S);   // S[query][key]
-        dP = DA_MFMA(da_rm(Gimg, KP, r, 16 * ks, hh), vfB[kt][ks], dP);  // dP[query][key]
+        S = DA_MFMA(da_rm(Qimg, KP, r, 16 * ks, hh), DQ ? da_rm(Kimg, KP, 32 * kt + r, 16 * ks, hh) : kfB[kt][ks], S);    // S[query][key]
+        dP = DA_MFMA(da_rm(Gimg, KP, r, 16 * ks, hh), DQ ? da_rm(Vimg, KP, 32 * kt + r, 16 * ks, hh) : vfB[kt][ks], dP);  // dP[query][key]
       }
       S = DA_MFMA(al, negB, S);
       dP = DA_MFMA(ad, negB, dP);
@@ -1103,35 +1162,32 @@ __global__ __launch_bounds__(256, DKV ? 1 : 2) void sra_bwd_kernel(SraArgs a) {
   }
   if (!DKV) return;
   // ---- the four waves meet in LDS: red[key][0..63] = dK (unscaled), red[key][64..127] = dV ----
-  // red[feature 0..127][key 0..63] (key fastest: a wave's 32 lanes hit 32 consecutive banks); the waves take turns, so
-  // plain read-modify-writes suffice
+  // Each wave writes its block red[wave][feature 0..127][key 0..63], all four at once (rows pitched by RP = 65 floats: a
+  // wave's 32 keys of one feature and, below, a wave's 64 features of one key both fall into distinct banks); then every
+  // thread adds the four values of its elements in the order wave 0, 1, 2, 3 — the order in which the waves used to take
+  // turns at one block, so the sum is the same float.
   float* red = (float*)lds;
-  __syncthreads();
-  for (int w = 0; w < 4; ++w) {
-    if (wave == w) {
+  __syncthreads();  // every wave is done with the images
+  {
+    float* mine = red + wave * RED;
 #pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
+    for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
+      for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const int key = 32 * kt + r, f = 32 * dt + da_row(i, hh);
-            if (w == 0) {
-              red[f * 64 + key] = dK[kt][dt][i];
-              red[(64 + f) * 64 + key] = dV[kt][dt][i];
-            } else {
-              red[f * 64 + key] += dK[kt][dt][i];
-              red[(64 + f) * 64 + key] += dV[kt][dt][i];
-            }
-          }
-    }
-    __syncthreads();
+        for (int i = 0; i < 16; ++i) {
+          const int key = 32 * kt + r, f = 32 * dt + da_row(i, hh);
+          mine[f * RP + key] = dK[kt][dt][i];
+          mine[(64 + f) * RP + key] = dV[kt][dt][i];
+        }
   }
+  __syncthreads();
   if (a.dkv_bf) {  // this workgroup saw every query of its (batch, head)
     bf* dkvb = a.dkv_bf + ((long)b * a.Nk + key0) * 2 * C + h * 64;
     for (int i = tid; i < Nk * 128; i += 256) {
       const int key = i >> 7, f = i & 127;
-      const float v = red[f * 64 + key];
+      const float* e = red + f * RP + key;
+      const float v = ((e[0] + e[RED]) + e[2 * RED]) + e[3 * RED];
       if (f < 64) stf(dkvb + (long)key * 2 * C + f, v * a.scale);
       else stf(dkvb + (long)key * 2 * C + C + (f - 64), v);
     }
@@ -1140,7 +1196,8 @@ __global__ __launch_bounds__(256, DKV ? 1 : 2) void sra_bwd_kernel(SraArgs a) {
   float* dkv = a.dkv + ((long)b * a.Nk + key0) * 2 * C + h * 64;
   for (int i = tid; i < Nk * 128; i += 256) {
     const int key = i >> 7, f = i & 127;  // 128 consecutive lanes = one key's 64 + 64 features: contiguous runs of 256 B
-    const float v = red[f * 64 + key];
+    const float* e = red + f * RP + key;
+    const float v = ((e[0] + e[RED]) + e[2 * RED]) + e[3 * RED];
     if (f < 64) atomicAdd(&dkv[(long)key * 2 * C + f], v * a.scale);
     else atomicAdd(&dkv[(long)key * 2 * C + C + (f - 64)], v);
   }
@@ -1176,21 +1233,21 @@ __global__ __launch_bounds__(256, 2) void sra_fwd_kernel(SraFwdArgs a) {
   const bf* vb = kb + C;
   bf* Kimg = lds;
   bf* Vimg = lds + KVIMG;
-  for (int id = tid; id < 2 * 64 * 8; id += 256) {
-    const int which = id >> 9, rem = id & 511, row = rem >> 3, c8 = rem & 7;
-    unsigned v4[4] = {0u, 0u, 0u, 0u};
-    if (row < Nk) memcpy(v4, (which ? vb : kb) + (long)row * 2 * C + 8 * c8, 16);
-    memcpy((which ? Vimg : Kimg) + row * KP + 8 * c8, v4, 16);
-  }
-  __syncthreads();
   const int q00 = (bid.x * 4 + wave) * 32 * a.tiles;
+  // the rows of a tile are fetched one trip ahead (tile 0: in front of the K / V chunks, landing with them), on every trip
+  da_u4 nx[4];
+  sra_fetch_q(nx, qb, q00 + r < Nq ? q00 + r : Nq - 1, C, hh);
+  sra_stage_kv<1, KP>(kb, vb, Nk, C, Kimg, tid);
+  __syncthreads();
+  da_loads_landed();
   for (int t = 0; t < a.tiles; ++t) {
     const int q0 = q00 + 32 * t;
     if (q0 >= Nq) break;  // (wave-uniform)
     const int qi = q0 + r < Nq ? q0 + r : Nq - 1;
     bf16x8 qf[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = da_ld8(qb + (long)qi * C + 16 * ks + 8 * hh, true);
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = da_frag(nx[ks]);
+    sra_fetch_q(nx, qb, q0 + 32 + r < Nq ? q0 + 32 + r : Nq - 1, C, hh);
     f32x16 S[2];
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
@@ -1271,12 +1328,15 @@ extern "C" int cenet_sra_attn_bwd_supported(int hd, int Nk) { return hd == 64 &&
 extern "C" int cenet_sra_attn_bwd_blocks_supported(int hd, int Nk) { return hd == 64 && Nk > 64 && Nk <= 256; }
 
 // 32-query tiles per wave: the kernel runs one workgroup per CU (484 registers), so more than 256 workgroups is a second
-// round; measured best (B = 32): 4 tiles at 3136 queries (42 us), 2 at 784 / 196 (31 us), 1 at 49 (25 us)
+// round; measured best (B = 32) when a tile cost five serial memory round trips: 4 tiles at 3136 queries (42 us), 2 at 784 / 196
+// (31 us), 1 at 49 (25 us).  With a tile's rows fetched one trip ahead the same launches take 27 / 19 / 13 us (DESIGN.md section 6,
+// round 10); the rule was not retuned.
 static int sra_tiles(int B, int H, int Nq) {
   int tiles = 1;
   while (tiles < 8 && (long)cdiv(Nq, 128 * tiles) * B * H > 256) ++tiles;
   return tiles;
 }
+extern "C" int cenet_sra_attn_bwd_tiles(int B, int H, int Nq) { return B > 0 && H > 0 && Nq > 0 ? sra_tiles(B, H, Nq) : 0; }
 // 1 when the launch for this problem puts every query of a (batch, head) in ONE workgroup: dK/dV then need no cross-workgroup
 // sum and cenet_sra_attn_bwd_direct_bf16 stores them as bf16 (the 14x14 and 7x7 stages of the ACDC preset)
 extern "C" int cenet_sra_attn_bwd_direct_supported(int B, int H, int Nq, int Nk) {

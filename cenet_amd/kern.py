@@ -359,6 +359,11 @@ def sra_attn_bwd_direct_supported(B, H, Nq, Nk) -> bool:
     return bool(_lib.lib().cenet_sra_attn_bwd_direct_supported(B, H, Nq, Nk))
 
 
+def sra_attn_bwd_tiles(B, H, Nq) -> int:
+    """32-query tiles per wave of the fused backward's launch for this problem (<= 64 keys)"""
+    return int(_lib.lib().cenet_sra_attn_bwd_tiles(B, H, Nq))
+
+
 def sra_attn_bwd_direct(q, kv, o, dout, lse, dq, dkv, B, H, Nq, Nk, scale):
     """as sra_attn_bwd where one workgroup owns a (batch, head): dkv bf16, written (not accumulated)"""
     _launch("cenet_sra_attn_bwd_direct_bf16", q, kv, o, dout, lse, dq, dkv, B, H, Nq, Nk, scale)

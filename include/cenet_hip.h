@@ -236,6 +236,8 @@ int cenet_sra_attn_bwd_bf16(const unsigned short* q, const unsigned short* kv, c
 /* The same kernel where its launch puts all queries of a (batch, head) in ONE workgroup (cenet_sra_attn_bwd_direct_supported:
  * the 14x14 and 7x7 stages at B = 32): dkv [B, Nk, 128 H] is written as bf16 directly — no zero fill, no atomics, no cast. */
 int cenet_sra_attn_bwd_direct_supported(int B, int H, int Nq, int Nk);
+/* 32-query tiles a wave of the Nk <= 64 backward launch walks through (workgroup = 4 waves = 128 * tiles queries). */
+int cenet_sra_attn_bwd_tiles(int B, int H, int Nq);
 int cenet_sra_attn_bwd_direct_bf16(const unsigned short* q, const unsigned short* kv, const unsigned short* o,
     const unsigned short* dout, const float* lse, unsigned short* dq, unsigned short* dkv, int B, int H, int Nq, int Nk,
     float scale, cenet_stream_t stream);

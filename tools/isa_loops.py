@@ -3,7 +3,7 @@
 
 Input: the `-S` output of a .hip file, e.g.
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-honor-nans --cuda-device-only -S cenet_amd/csrc/attn_diff.hip -o attn_diff.s
-    python3 tools/isa_loops.py attn_diff.s [--match dattn_] [--md]
+    python3 tools/isa_loops.py attn_diff.s [--match dattn_] [--md] [--all-loops]
 
 Per kernel it prints the resource lines (VGPR + AGPR, scratch bytes, waves per SIMD) and, per loop that holds an `s_barrier`
 (the cycle of basic blocks around it), the events in program order in compact form:
@@ -13,6 +13,8 @@ Per kernel it prints the resource lines (VGPR + AGPR, scratch bytes, waves per S
 A loop is FLAGGED (`DRAIN`) when a vmcnt wait follows a load and precedes an MFMA inside one trip: the wait then stands between
 the prefetch and the tile body, so the loads it waits for cannot overlap the body.  A register prefetch is right when the
 loop reads  L<n> M<m> W S<k> B : all loads first, one wait in front of the LDS writes.
+--all-loops lists the loops without an `s_barrier` too (the sra_* tile loops order their LDS traffic with wave barriers alone; a
+staging loop that was not unrolled), in the same notation, a trip starting at the loop's first block in the listing.
 """
 import argparse
 import re
@@ -59,10 +61,12 @@ def kernels(text):
         i += 1
 
 
-def barrier_loops(body):
+def barrier_loops(body, all_loops=False):
     """Loops that hold an s_barrier: the strongly connected components of the block graph (branch targets + fall-through) with a
     barrier inside.  (Not the compiler's `in Loop: Header=` comments: a loop entered at two blocks is irreducible and gets none.)
-    Returns [(label of the first block, instructions of one trip, from behind the barrier to the barrier)]."""
+    Returns [(label of the first block, instructions of one trip, from behind the barrier to the barrier)].
+    all_loops: the components without a barrier as well (a loop that synchronises with wave barriers alone, a staging loop),
+    in listing order; one trip of such a loop runs from its first block in the listing, the loop's header, around to it."""
     blocks = [["entry", []]]
     for raw in body:
         s = raw.strip()
@@ -96,8 +100,11 @@ def barrier_loops(body):
     every = set(range(len(blocks)))
     pred = [[p for p in every if n in succ[p]] for n in every]
     out, done = [], set()
-    for n, (_, ins) in enumerate(blocks):
-        if n in done or not any(i.startswith("s_barrier") for i in ins):
+    starts = [n for n, (_, ins) in enumerate(blocks) if any(i.startswith("s_barrier") for i in ins)]
+    if all_loops:  # barrier blocks first, so that a loop with a barrier keeps its barrier-to-barrier trip
+        starts += list(range(len(blocks)))
+    for n in starts:
+        if n in done:
             continue
         fwd = reach(n, every)
         if n not in fwd:
@@ -123,9 +130,12 @@ def barrier_loops(body):
         for t in reversed(succ[n]):
             if t in inside and t not in seen:
                 walk(t)
-        order = post[::-1] + [n]
-        out.append((blocks[order[0]][0], [i for b in order for i in blocks[b][1]]))
-    return out
+        if any(i.startswith("s_barrier") for i in blocks[n][1]):
+            order = post[::-1] + [n]
+        else:  # (scc[0] == n: the blocks are visited in listing order and n is the first of its component not done)
+            order = [n] + post[::-1]
+        out.append((order[0], blocks[order[0]][0], [i for b in order for i in blocks[b][1]]))
+    return [(label, ins) for _, label, ins in sorted(out)]
 
 
 def shape(ins):
@@ -179,6 +189,8 @@ def main():
     ap.add_argument("asm")
     ap.add_argument("--match", default="", help="only kernels whose demangled name contains this")
     ap.add_argument("--md", action="store_true", help="markdown table rows")
+    ap.add_argument("--all-loops", action="store_true",
+                    help="also the loops without an s_barrier (a trip then starts at the loop's first block in the listing)")
     a = ap.parse_args()
     text = open(a.asm).read()
     ks = list(kernels(text))
@@ -191,7 +203,7 @@ def main():
         name = names[sym].replace("void ", "").replace("(DiffArgs)", "")
         if a.match not in name:
             continue
-        loops = barrier_loops(body)
+        loops = barrier_loops(body, a.all_loops)
         regs = "%d+%d" % (res.get("NumVgprs", -1), res.get("NumAgprs", 0))
         head = (name, regs, res.get("ScratchSize", -1), res.get("Occupancy", -1))
         if not loops:
