@@ -1187,6 +1187,59 @@ def dist_loss_bwd(logits, labels, d2g, d2p, w, gout, dlogits, B, K, H, W, surfac
           int(bool(surface)), int(bool(hausdorff)))
 
 
+def lovasz_tile() -> int:
+    """elements per tile of the radix sort of csrc/lovasz.hip"""
+    return _lib.lib().cenet_lovasz_tile()
+
+
+def _lovasz_shape(B, K, H, W, per_image):
+    S, n = (B * K, H * W) if per_image else (K, B * H * W)
+    if not 2 <= K <= 16 or B < 1 or H < 1 or W < 1 or S > 65535 or n >= 2 ** 31:
+        raise ValueError(f"lovasz: unsupported shape B={B} K={K} H={H} W={W} per_image={bool(per_image)} "
+                         f"(2 <= K <= 16, at most 65535 segments of fewer than 2^31 pixels)")
+
+
+def lovasz_ws_bytes(B, K, H, W, per_image) -> int:
+    """bytes of workspace cenet_lovasz_fwd needs: keys and payloads twice, the digit counts of a pass, the g counts, the loss rows"""
+    _lovasz_shape(B, K, H, W, per_image)
+    return _lib.lib().cenet_lovasz_ws_bytes(B, K, H, W, int(bool(per_image)))
+
+
+def lovasz_order_ws_bytes(S, n) -> int:
+    if not (1 <= S <= 65535 and 1 <= n < 2 ** 31):
+        raise ValueError(f"lovasz_order: 1 <= S <= 65535 segments of 1 <= n < 2^31 elements expected, got S={S} n={n}")
+    return _lib.lib().cenet_lovasz_order_ws_bytes(S, n)
+
+
+def lovasz_order(errors_f32, ws, perm_i32, S, n):
+    """perm [S,n] int32 = the stable descending order of errors [S,n] (fp32, non-negative): numpy's argsort(-e, kind="stable")"""
+    lovasz_order_ws_bytes(S, n)
+    if errors_f32.numel() != S * n or perm_i32.numel() != S * n:
+        raise ValueError(f"lovasz_order: tensor sizes do not match {(S, n)}")
+    _call("cenet_lovasz_order_f32", errors_f32, ws, ws.numel() * ws.element_size(), perm_i32, S, n)
+
+
+def lovasz_fwd(inputs, labels, ws, coef, loss, B, K, H, W, per_image, classes_all, ignore_index, from_probs):
+    """loss[0] = the Lovasz-Softmax loss, coef [B,K,H,W] fp32 = dloss / dp (include/cenet_hip.h spells both out);
+    ignore_index: None or the label that is in no class"""
+    _lovasz_shape(B, K, H, W, per_image)
+    if inputs.numel() != B * K * H * W or labels.numel() != B * H * W or coef.numel() != inputs.numel():
+        raise ValueError(f"lovasz: tensor sizes do not match {(B, K, H, W)}")
+    _call("cenet_lovasz_fwd_f32", inputs, labels, ws, ws.numel() * ws.element_size(), coef, loss, B, K, H, W,
+          int(bool(per_image)), int(bool(classes_all)), int(ignore_index is not None),
+          0 if ignore_index is None else int(ignore_index), int(bool(from_probs)))
+
+
+def lovasz_bwd(inputs, coef, gout, dinputs, B, K, H, W, from_probs):
+    if not 2 <= K <= 16 or B < 1 or H < 1 or W < 1:
+        raise ValueError(f"lovasz: unsupported shape B={B} K={K} H={H} W={W} (2 <= K <= 16)")
+    if inputs.numel() != B * K * H * W or coef.numel() != inputs.numel():
+        raise ValueError(f"lovasz: tensor sizes do not match {(B, K, H, W)}")
+    if dinputs.numel() != inputs.numel() or _overlap(dinputs, inputs):
+        raise ValueError("lovasz: dinputs has the inputs' size and may not alias them")
+    _call("cenet_lovasz_bwd_f32", inputs, coef, gout, dinputs, B, K, H, W, int(bool(from_probs)))
+
+
 def sgd_step(p, g, buf, hyper5, n, shadow=None):
     """shadow: bf16 copy of the parameters, rewritten by the same kernel (the GEMM operand of the throughput mode)"""
     if shadow is None:

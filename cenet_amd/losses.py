@@ -12,6 +12,10 @@ The distance-map losses `surface` (Kervadec et al. 2019) and `hausdorff` (Karimi
 cenet_amd.ops.dist_loss: the exact distance maps of every label map (and, for `hausdorff`, of the thresholded prediction) are
 built on the device inside the step (csrc/edt.hip) and one fused kernel each way reads them (csrc/dist_loss.hip).  They are
 not in the reference; a Criterion that names neither launches nothing of this.
+
+`lovasz` (LovaszSoftmaxLoss; Berman, Triki, Blaschko 2018) goes through cenet_amd.ops.lovasz_softmax: the loss that optimises
+the Jaccard index itself needs every pixel's rank among the errors of its class, which csrc/lovasz.hip gets from a batched stable
+radix sort on the device.  Not in the reference either, and a Criterion that does not name it launches nothing of it.
 """
 from __future__ import annotations
 
@@ -84,6 +88,22 @@ class HausdorffDTLoss(nn.Module):
         return ops.dist_loss(inputs, target, (0.0, 1.0), surface=False, hausdorff=True)
 
 
+class LovaszSoftmaxLoss(nn.Module):
+    """The Lovasz-Softmax loss of Berman, Triki, Blaschko 2018 (Alg. 1), the tight convex surrogate of the Jaccard index: per
+    class the errors |[target == c] - softmax_c| in descending order, weighted by the increments of the Jaccard loss along that
+    order.  classes: "present" (mean over the classes that occur) or "all"; per_image: per image, then the mean over the images;
+    ignore_index: that label is in no class.  inputs [B,K,H,W] logits, target [B,H,W] class ids as floats."""
+
+    def __init__(self, per_image=False, classes="present", ignore_index=None):
+        super().__init__()
+        if classes not in ("present", "all"):
+            raise ValueError(f"LovaszSoftmaxLoss: classes is 'present' or 'all', got {classes!r}")
+        self.per_image, self.classes, self.ignore_index = bool(per_image), classes, ignore_index
+
+    def forward(self, inputs, target):
+        return ops.lovasz_softmax(inputs, target, per_image=self.per_image, classes=self.classes, ignore_index=self.ignore_index)
+
+
 def _class_weights(value, K, name):
     """None, a comma string or a sequence of K floats -> None or a list of K floats"""
     if value is None:
@@ -104,7 +124,10 @@ class Criterion(nn.Module):
     `surface` and `hausdorff` (SurfaceLoss, HausdorffDTLoss) are two more loss names: their term is added to the total of the
     other names (which is not computed when none of them is named).  Their weights live in the buffer `dist_weights` ([2]:
     surface, hausdorff), read on the device by every call; set_dist_weights() writes into it without a sync, so a weight
-    schedule costs a captured step no recapture.  Either name with ignore_index is refused, as boundary is."""
+    schedule costs a captured step no recapture.  Either name with ignore_index is refused, as boundary is.
+    `lovasz` (LovaszSoftmaxLoss) is one more name whose term, times its weight of loss_weights, is added in the same way; it
+    honours ignore_index and reads two more optional attributes, lovasz_per_image (default False) and lovasz_classes (default
+    "present").  A Criterion that does not name it calls nothing of it."""
 
     def __init__(self, num_classes, args):
         super().__init__()
@@ -115,7 +138,11 @@ class Criterion(nn.Module):
         has_jaccard = False
         self.has_base = self.has_surface = self.has_hausdorff = False
         w_dist = [0.0, 0.0]
+        self.has_lovasz, self.w_lovasz = False, 0.0
         for n, w in zip(names, weights):
+            if n == "lovasz":
+                self.has_lovasz, self.w_lovasz = True, self.w_lovasz + w
+                continue
             if n in ("surface", "hausdorff"):
                 w_dist[1 if n == "hausdorff" else 0] += w
                 self.has_surface = self.has_surface or n == "surface"
@@ -146,6 +173,10 @@ class Criterion(nn.Module):
         if self.ignore_index is not None and (self.has_surface or self.has_hausdorff):
             raise NotImplementedError("Loss surface / hausdorff with ignore_index not implemented: a distance map over a label "
                                       "mask with holes is not defined")
+        self.lovasz_per_image = bool(getattr(args, "lovasz_per_image", False))
+        self.lovasz_classes = getattr(args, "lovasz_classes", None) or "present"
+        if self.has_lovasz and self.lovasz_classes not in ("present", "all"):
+            raise ValueError(f"lovasz_classes is 'present' or 'all', got {self.lovasz_classes!r}")
         if self.has_surface or self.has_hausdorff:
             self.register_buffer("dist_weights", torch.tensor(w_dist, dtype=torch.float32))
         else:
@@ -169,6 +200,14 @@ class Criterion(nn.Module):
                     self.dist_weights[i].fill_(float(v))
 
     def forward(self, outputs, labels):
+        if not self.has_lovasz:
+            return self._named(outputs, labels)
+        lovasz = self.w_lovasz * ops.lovasz_softmax(outputs, labels, per_image=self.lovasz_per_image, classes=self.lovasz_classes,
+                                                    ignore_index=self.ignore_index)
+        return self._named(outputs, labels) + lovasz if self.has_base or self.dist_weights is not None else lovasz
+
+    def _named(self, outputs, labels):
+        """the total of every name but `lovasz`"""
         if self.dist_weights is None:
             return self._base(outputs, labels)
         dist = ops.dist_loss(outputs, labels, self.dist_weights, surface=self.has_surface, hausdorff=self.has_hausdorff)

@@ -273,5 +273,62 @@ def dist_loss(logits, labels, weights, *, surface=True, hausdorff=True):
     return DistLossFn.apply(logits, labels.float(), w, bool(surface), bool(hausdorff))
 
 
+# =====================================================================================================
+# Lovasz-Softmax (Berman, Triki, Blaschko 2018; csrc/lovasz.hip; not in the reference)
+# =====================================================================================================
+class LovaszFn(Function):
+    """The Lovasz-Softmax loss (include/cenet_hip.h spells it out).  Forward: keys, the batched radix sort, integer ranks and the
+    coefficients a = dloss / dp [B,K,H,W] fp32, which the backward — one launch — applies.  The workspace comes from the caching
+    allocator and is free again after the forward; nothing synchronises.  The gradient goes to `inputs` only."""
+
+    @staticmethod
+    def forward(ctx, inputs, target, per_image, classes_all, ignore_index, from_probs):
+        inputs, target = _c(inputs), _c(target)
+        B, K, H, W = inputs.shape
+        ws = _empty((kern.lovasz_ws_bytes(B, K, H, W, per_image) // 4,), inputs, torch.int32)
+        coef = _empty((B, K, H, W), inputs)
+        loss = _empty((1,), inputs)
+        kern.lovasz_fwd(inputs, target, ws, coef, loss, B, K, H, W, per_image, classes_all, ignore_index, from_probs)
+        ctx.save_for_backward(inputs, coef)
+        ctx.from_probs = from_probs
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        inputs, coef = ctx.saved_tensors
+        B, K, H, W = inputs.shape
+        d = torch.empty_like(inputs)
+        kern.lovasz_bwd(inputs, coef, _c(g).reshape(1).float(), d, B, K, H, W, ctx.from_probs)
+        return d, None, None, None, None, None
+
+
+def lovasz_softmax(inputs, target, *, per_image=False, classes="present", ignore_index=None, from_probs=False):
+    """The Lovasz-Softmax loss on inputs [B,K,H,W] (fp32 or bf16 logits; probabilities with from_probs) and target [B,H,W] (class
+    ids as floats): per class the pixels ordered by descending error |[target == c] - p_c| — equal errors by ascending pixel
+    index, so the result is a function of the inputs alone — and the errors weighted by the increments of the Jaccard loss along
+    that order.  classes: "present" (the mean over the classes that occur in the labels) or "all"; per_image: the loss of every
+    image on its own, then the mean over the images; ignore_index: pixels with that label are in no class and get no gradient."""
+    if classes not in ("present", "all"):
+        raise ValueError(f"lovasz_softmax: classes is 'present' or 'all', got {classes!r}")
+    if inputs.dim() != 4 or target.shape != (inputs.shape[0],) + tuple(inputs.shape[2:]):
+        raise ValueError(f"lovasz_softmax: inputs [B,K,H,W] and target [B,H,W] expected, got {tuple(inputs.shape)} and "
+                         f"{tuple(target.shape)}")
+    return LovaszFn.apply(inputs, target.float(), bool(per_image), classes == "all",
+                          None if ignore_index is None else int(ignore_index), bool(from_probs))
+
+
+def lovasz_order(errors: Tensor) -> Tensor:
+    """errors [S,n] fp32, non-negative -> int32 [S,n]: the stable descending order of every row, numpy's
+    argsort(-errors, kind="stable") — the sort of lovasz_softmax on its own"""
+    if errors.dim() != 2 or errors.dtype != torch.float32:
+        raise ValueError(f"lovasz_order: errors [S,n] fp32 expected, got {errors.dtype} {tuple(errors.shape)}")
+    S, n = errors.shape
+    errors = _c(errors)
+    ws = _empty((kern.lovasz_order_ws_bytes(S, n) // 4,), errors, torch.int32)
+    perm = _empty((S, n), errors, torch.int32)
+    kern.lovasz_order(errors, ws, perm, S, n)
+    return perm
+
+
 __all__ = ["DsebCombineFn", "dseb_combine", "DiceCELossFn", "dice_ce_loss", "SegLossExFn", "class_weight_buffer", "seg_loss",
-           "distance_maps", "pred_distance_maps", "DistLossFn", "dist_loss"]
+           "distance_maps", "pred_distance_maps", "DistLossFn", "dist_loss", "LovaszFn", "lovasz_softmax", "lovasz_order"]

@@ -36,10 +36,10 @@ def _as_batches(loader) -> Iterable[dict]:
 
 
 def criterion_args(loss_type: str = "dice,ce", loss_weights: str = "0.5,0.5", dice_class_weights=None, ce_class_weights=None,
-                   ignore_index=None) -> argparse.Namespace:
+                   ignore_index=None, lovasz_per_image=False) -> argparse.Namespace:
     """the `args` train_acdc hands losses.Criterion"""
     return argparse.Namespace(loss_type=loss_type, loss_weights=loss_weights, dice_class_weights=dice_class_weights,
-                              ce_class_weights=ce_class_weights, ignore_index=ignore_index)
+                              ce_class_weights=ce_class_weights, ignore_index=ignore_index, lovasz_per_image=lovasz_per_image)
 
 
 def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, base_lr: float = 0.05, momentum: float = 0.9,
@@ -49,7 +49,7 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
                test_volumes: Optional[Callable[[], Iterable]] = None, save_dir: Optional[str] = None, img_size: int = 224,
                test_resize: str = "device", dice_class_weights=None, ce_class_weights=None, ignore_index=None,
                test_postprocess=None, dist_weight_schedule: Optional[Callable[[int], tuple]] = None, test_tta=None,
-               test_spacing=None, test_nsd_tolerance=None) -> dict:
+               test_spacing=None, test_nsd_tolerance=None, lovasz_per_image=False) -> dict:
     """main_acdc.py:200-290.  tr_loader yields {'image' [B,C,H,W] float (C = the network's input channels), 'label' [B,H,W]} batches (host or device tensors);
     val_batches() yields (image [1,1,H,W], label [1,H,W]) pairs for the per-epoch validation (main_acdc.py:218-231).
     optimizer / scheduler: the reference's --optimizer / --scheduler strings (main_acdc.py:34-35, core.py:12-41); `momentum`
@@ -69,7 +69,9 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
     loss_type may also name `surface` and `hausdorff` (the distance-map losses, their weights in loss_weights);
     dist_weight_schedule: epoch -> (w_surface, w_hausdorff), called at the start of every epoch and handed to
     Criterion.set_dist_weights — the weights are read on the device, so the captured step is replayed, not recaptured
-    (Kervadec's rebalancing moves the surface weight every epoch)"""
+    (Kervadec's rebalancing moves the surface weight every epoch)
+    loss_type may name `lovasz` too (the Lovasz-Softmax loss, its weight in loss_weights; lovasz_per_image: every image on its
+    own): sort, ranks and coefficients are launches of the captured step like any other"""
     import os
 
     from . import checkpoint, evaluate
@@ -85,7 +87,7 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
     dev = torch.device(device)
     net = net.to(dev).train()
     crit = losses.Criterion(num_classes, criterion_args(loss_type, loss_weights, dice_class_weights, ce_class_weights,
-                                                        ignore_index)).to(dev)
+                                                        ignore_index, lovasz_per_image)).to(dev)
     if dist_weight_schedule is not None and crit.dist_weights is None:
         raise ValueError("dist_weight_schedule: loss_type names neither surface nor hausdorff")
     arena = optim.ParamArena(net, optim.cenet_segments())

@@ -683,6 +683,39 @@ int cenet_dist_loss_fwd_f32(const float* logits, const float* labels, const int*
 int cenet_dist_loss_bwd_f32(const float* logits, const float* labels, const int* d2g, const int* d2p, const float* w,
                             const float* gout, float* dlogits, int B, int K, int H, int W, int surface, int hausdorff,
                             cenet_stream_t stream);
+/* The Lovasz-Softmax loss (Berman, Triki, Blaschko, CVPR 2018, Alg. 1; csrc/lovasz.hip; not in the reference).  inputs [B,K,H,W]
+ * logits, or probabilities with from_probs; labels [B,H,W] class ids as floats.  p = softmax(inputs) over K in fp32 (from_probs:
+ * p = inputs), g = [label == c], e = |g - p_c| in fp32.  A SEGMENT is one class over all n = B H W pixels (S = K segments) or, with
+ * per_image, one (image, class) with n = H W (S = B K).  Inside a segment the pixels are ordered by descending e, equal e by
+ * ascending pixel index (b, h, w): a stable descending sort, so the result is a function of the inputs alone.  All counts are
+ * integers: G = pixels with g = 1 in the segment; at sorted position i (from 0) F_i = those among positions 0 .. i, Z_i = the
+ * g = 0 among them, I_i = G - F_i, U_i = G + Z_i, J_i = 1 - I_i / U_i, J_{-1} = 0.  The increment J_i - J_{i-1} is evaluated as
+ *   1 / U_i  (g = 1)       I_i / (U_i (U_i - 1))  (g = 0)       1  (U_i = 1: i = 0 in a segment with G = 0)
+ * from the integers, never as a difference of two numbers near 1.  Segment loss L = sum_i e_(i) (J_i - J_{i-1});
+ *   loss = the mean of L over the segments with G > 0 (classes_all: over all K), with per_image per image, then over the B images
+ * (the divisor is computed on the device; no segment that counts: 0).  coef [B,K,H,W] fp32 = a = dloss / dp_c(x) =
+ * s (J_i - J_{i-1}) / divisor, s = -1 for g = 1, +1 for g = 0, 0 where e == 0 exactly (the gradient of |.|).  has_ignore: a pixel
+ * whose label is ignore_index is in no class and no count, sorts below every other pixel and has a = 0.
+ * Forward: keys (bits of e, + 1; 0 = ignored) and payloads (pixel index, g bit), a batched stable LSD radix sort over the segments
+ * (8 bits a pass, tiles of cenet_lovasz_tile() elements, ranks inside a tile by ballots: no atomic decides an order), an integer
+ * scan of the g bits along the sorted order (G is that scan's total over the segment: the keys pass counts nothing), the
+ * coefficients, one partial sum per workgroup stored in ws and a one-workgroup launch
+ * that adds them in a fixed order — no float atomics, bitwise reproducible.  ws: ws_bytes >= cenet_lovasz_ws_bytes(B, K, H, W,
+ * per_image) bytes of scratch, 4-byte aligned.  Backward, one launch: dinputs_j = gout[0] p_j (a_j - sum_c p_c a_c), from_probs:
+ * gout[0] a_j; dinputs may not be inputs.  CENET_EINVAL (nothing launched) unless 2 <= K <= 16, B, H, W >= 1, S <= 65535,
+ * n < 2^31 and the workspace is large enough.
+ * cenet_lovasz_order_f32 is the sort alone: errors [S, n] fp32, non-negative -> perm [S, n] int32, perm[s][i] = the index in
+ * segment s of the element at sorted position i (numpy: argsort(-e, kind="stable")); ws_bytes >= cenet_lovasz_order_ws_bytes(S, n);
+ * CENET_EINVAL unless 1 <= S <= 65535 and 1 <= n < 2^31. */
+int cenet_lovasz_tile(void);
+long cenet_lovasz_ws_bytes(int B, int K, int H, int W, int per_image);
+long cenet_lovasz_order_ws_bytes(int S, int n);
+int cenet_lovasz_order_f32(const float* errors, void* ws, long ws_bytes, int* perm, int S, int n, cenet_stream_t stream);
+int cenet_lovasz_fwd_f32(const float* inputs, const float* labels, void* ws, long ws_bytes, float* coef, float* loss, int B, int K,
+                         int H, int W, int per_image, int classes_all, int has_ignore, int ignore_index, int from_probs,
+                         cenet_stream_t stream);
+int cenet_lovasz_bwd_f32(const float* inputs, const float* coef, const float* gout, float* dinputs, int B, int K, int H, int W,
+                         int from_probs, cenet_stream_t stream);
 /* torch.optim.SGD(momentum, weight_decay) over a flat arena; hyper5 (device) = [lr, momentum, wd, grad_scale, first_step] */
 int cenet_sgd_step_f32(float* p, const float* g, float* buf, const float* hyper5, long n, cenet_stream_t stream);
 /* torch.optim.Adam / AdamW (amsgrad off) over a flat arena, one pass; exp_avg / exp_avg_sq are the flat fp32 moment buffers.
@@ -798,6 +831,12 @@ int cenet_dist_loss_fwd_bf16(const unsigned short* logits, const float* labels, 
     float* ws, long ws_floats, float* loss, int B, int K, int H, int W, int surface, int hausdorff, cenet_stream_t stream);
 int cenet_dist_loss_bwd_bf16(const unsigned short* logits, const float* labels, const int* d2g, const int* d2p, const float* w,
     const float* gout, unsigned short* dlogits, int B, int K, int H, int W, int surface, int hausdorff, cenet_stream_t stream);
+/* lovasz.hip */
+int cenet_lovasz_fwd_bf16(const unsigned short* inputs, const float* labels, void* ws, long ws_bytes, float* coef, float* loss,
+    int B, int K, int H, int W, int per_image, int classes_all, int has_ignore, int ignore_index, int from_probs,
+    cenet_stream_t stream);
+int cenet_lovasz_bwd_bf16(const unsigned short* inputs, const float* coef, const float* gout, unsigned short* dinputs, int B,
+    int K, int H, int W, int from_probs, cenet_stream_t stream);
 /* norm.hip */
 int cenet_layernorm_fwd_bf16(const unsigned short* x, const float* gamma, const float* beta, unsigned short* y, float* mean,
     float* rstd, int rows, int C, float eps, cenet_stream_t stream);
