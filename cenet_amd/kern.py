@@ -1240,6 +1240,60 @@ def lovasz_bwd(inputs, coef, gout, dinputs, B, K, H, W, from_probs):
     _call("cenet_lovasz_bwd_f32", inputs, coef, gout, dinputs, B, K, H, W, int(bool(from_probs)))
 
 
+def topk_tile() -> int:
+    """elements per tile of the tie rank of csrc/topk_ce.hip"""
+    return _lib.lib().cenet_topk_tile()
+
+
+def _topk_shape(B, K, H, W, per_image):
+    S, n = (B, H * W) if per_image else (1, B * H * W)
+    if not 2 <= K <= 16 or B < 1 or H < 1 or W < 1 or S > 65535 or n >= 2 ** 31:
+        raise ValueError(f"topk_ce: unsupported shape B={B} K={K} H={H} W={W} per_image={bool(per_image)} "
+                         f"(2 <= K <= 16, at most 65535 segments of fewer than 2^31 pixels)")
+
+
+def topk_ce_ws_bytes(B, H, W, per_image) -> int:
+    """bytes of workspace cenet_topk_ce_fwd needs: the keys, the digit bins of the four rounds, the tie counts, the loss rows"""
+    _topk_shape(B, 2, H, W, per_image)
+    return _lib.lib().cenet_topk_ce_ws_bytes(B, H, W, int(bool(per_image)))
+
+
+def topk_mask_ws_bytes(S, n) -> int:
+    if not (1 <= S <= 65535 and 1 <= n < 2 ** 31):
+        raise ValueError(f"topk_mask: 1 <= S <= 65535 segments of 1 <= n < 2^31 elements expected, got S={S} n={n}")
+    return _lib.lib().cenet_topk_mask_ws_bytes(S, n)
+
+
+def topk_mask(values_f32, m_i32, ws, mask_u8, S, n):
+    """mask [S,n] uint8 = 1 on the m[s] largest of values [S,n] (fp32, non-negative), equal values by ascending index: numpy's
+    argsort(-v, kind="stable")[:m]"""
+    topk_mask_ws_bytes(S, n)
+    if values_f32.numel() != S * n or mask_u8.numel() != S * n or m_i32.numel() != S:
+        raise ValueError(f"topk_mask: tensor sizes do not match {(S, n)}")
+    _call("cenet_topk_mask_f32", values_f32, m_i32, ws, ws.numel() * ws.element_size(), mask_u8, S, n)
+
+
+def topk_ce_fwd(logits, labels, kpercent, ws, wgt, loss, B, K, H, W, per_image, ignore_index):
+    """loss[0] = the top-k cross-entropy, wgt [B,H,W] fp32 = 1 / (m S_valid) on the kept pixels (include/cenet_hip.h spells both
+    out); kpercent: one fp32 on the device, read there; ignore_index: None or the label that is in no count"""
+    _topk_shape(B, K, H, W, per_image)
+    if logits.numel() != B * K * H * W or labels.numel() != B * H * W or wgt.numel() != B * H * W or kpercent.numel() != 1:
+        raise ValueError(f"topk_ce: tensor sizes do not match {(B, K, H, W)}")
+    _call("cenet_topk_ce_fwd_f32", logits, labels, kpercent, ws, ws.numel() * ws.element_size(), wgt, loss, B, K, H, W,
+          int(bool(per_image)), int(ignore_index is not None), 0 if ignore_index is None else int(ignore_index))
+
+
+def topk_ce_bwd(logits, labels, wgt, gout, dlogits, B, K, H, W, ignore_index):
+    if not 2 <= K <= 16 or B < 1 or H < 1 or W < 1:
+        raise ValueError(f"topk_ce: unsupported shape B={B} K={K} H={H} W={W} (2 <= K <= 16)")
+    if logits.numel() != B * K * H * W or labels.numel() != B * H * W or wgt.numel() != B * H * W:
+        raise ValueError(f"topk_ce: tensor sizes do not match {(B, K, H, W)}")
+    if dlogits.numel() != logits.numel() or _overlap(dlogits, logits):
+        raise ValueError("topk_ce: dlogits has the logits' size and may not alias them")
+    _call("cenet_topk_ce_bwd_f32", logits, labels, wgt, gout, dlogits, B, K, H, W, int(ignore_index is not None),
+          0 if ignore_index is None else int(ignore_index))
+
+
 def sgd_step(p, g, buf, hyper5, n, shadow=None):
     """shadow: bf16 copy of the parameters, rewritten by the same kernel (the GEMM operand of the throughput mode)"""
     if shadow is None:

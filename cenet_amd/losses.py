@@ -16,6 +16,10 @@ not in the reference; a Criterion that names neither launches nothing of this.
 `lovasz` (LovaszSoftmaxLoss; Berman, Triki, Blaschko 2018) goes through cenet_amd.ops.lovasz_softmax: the loss that optimises
 the Jaccard index itself needs every pixel's rank among the errors of its class, which csrc/lovasz.hip gets from a batched stable
 radix sort on the device.  Not in the reference either, and a Criterion that does not name it launches nothing of it.
+
+`topk` (TopKCrossEntropyLoss; hard-pixel mining, the CE half of nnU-Net's DC_and_topk_loss) goes through cenet_amd.ops.topk_ce:
+the cross-entropy averaged over the k % of pixels with the largest loss, which csrc/topk_ce.hip finds with a radix select on the
+device.  Not in the reference, and a Criterion that does not name it launches nothing of it.
 """
 from __future__ import annotations
 
@@ -104,6 +108,24 @@ class LovaszSoftmaxLoss(nn.Module):
         return ops.lovasz_softmax(inputs, target, per_image=self.per_image, classes=self.classes, ignore_index=self.ignore_index)
 
 
+class TopKCrossEntropyLoss(nn.Module):
+    """The top-k cross-entropy: the mean of the cross-entropy over the k % of the valid pixels with the largest loss (at least
+    one), equal losses by ascending pixel index.  k: a percentage, 0 < k <= 100, kept in the buffer `percent` ([1] fp32, follows
+    .to()) and read on the device; per_image: every image on its own, then the mean over the images; ignore_index: that label
+    is in no count.  No class weights, no probability threshold (OHEM's thresh / min_kept), logits only.
+    inputs [B,K,H,W] logits, target [B,H,W] class ids as floats."""
+
+    def __init__(self, k=10.0, per_image=False, ignore_index=None):
+        super().__init__()
+        if not 0.0 < float(k) <= 100.0:
+            raise ValueError(f"TopKCrossEntropyLoss: k is a percentage, 0 < k <= 100, got {k}")
+        self.per_image, self.ignore_index = bool(per_image), ignore_index
+        self.register_buffer("percent", torch.tensor([float(k)], dtype=torch.float32))
+
+    def forward(self, inputs, target):
+        return ops.topk_ce(inputs, target, self.percent, per_image=self.per_image, ignore_index=self.ignore_index)
+
+
 def _class_weights(value, K, name):
     """None, a comma string or a sequence of K floats -> None or a list of K floats"""
     if value is None:
@@ -127,7 +149,10 @@ class Criterion(nn.Module):
     schedule costs a captured step no recapture.  Either name with ignore_index is refused, as boundary is.
     `lovasz` (LovaszSoftmaxLoss) is one more name whose term, times its weight of loss_weights, is added in the same way; it
     honours ignore_index and reads two more optional attributes, lovasz_per_image (default False) and lovasz_classes (default
-    "present").  A Criterion that does not name it calls nothing of it."""
+    "present").  A Criterion that does not name it calls nothing of it.
+    `topk` (TopKCrossEntropyLoss) is added the same way; it honours ignore_index and reads topk_percent (default 10.0) and
+    topk_per_image (default False).  The percentage lives in the buffer `topk_percent` ([1] fp32), read on the device by every
+    call; set_topk_percent() writes into it without a sync, so a schedule costs a captured step no recapture."""
 
     def __init__(self, num_classes, args):
         super().__init__()
@@ -139,7 +164,11 @@ class Criterion(nn.Module):
         self.has_base = self.has_surface = self.has_hausdorff = False
         w_dist = [0.0, 0.0]
         self.has_lovasz, self.w_lovasz = False, 0.0
+        self.has_topk, self.w_topk = False, 0.0
         for n, w in zip(names, weights):
+            if n == "topk":
+                self.has_topk, self.w_topk = True, self.w_topk + w
+                continue
             if n == "lovasz":
                 self.has_lovasz, self.w_lovasz = True, self.w_lovasz + w
                 continue
@@ -177,6 +206,15 @@ class Criterion(nn.Module):
         self.lovasz_classes = getattr(args, "lovasz_classes", None) or "present"
         if self.has_lovasz and self.lovasz_classes not in ("present", "all"):
             raise ValueError(f"lovasz_classes is 'present' or 'all', got {self.lovasz_classes!r}")
+        self.topk_per_image = bool(getattr(args, "topk_per_image", False))
+        percent = getattr(args, "topk_percent", None)
+        percent = 10.0 if percent is None else float(percent)
+        if self.has_topk:
+            if not 0.0 < percent <= 100.0:
+                raise ValueError(f"topk_percent is a percentage, 0 < k <= 100, got {percent}")
+            self.register_buffer("topk_percent", torch.tensor([percent], dtype=torch.float32))
+        else:
+            self.topk_percent = None
         if self.has_surface or self.has_hausdorff:
             self.register_buffer("dist_weights", torch.tensor(w_dist, dtype=torch.float32))
         else:
@@ -199,7 +237,29 @@ class Criterion(nn.Module):
                 elif v is not None:
                     self.dist_weights[i].fill_(float(v))
 
+    def set_topk_percent(self, v):
+        """a new percentage of the `topk` term (a number in (0, 100], or a one-element tensor), written into `topk_percent` on its
+        device by one launch: no sync, and the next call — a graph replay included — reads it"""
+        if self.topk_percent is None:
+            raise ValueError("set_topk_percent: loss_type does not name topk")
+        with torch.no_grad():
+            if isinstance(v, torch.Tensor):
+                self.topk_percent.copy_(v.reshape(1), non_blocking=True)
+            else:
+                if not 0.0 < float(v) <= 100.0:
+                    raise ValueError(f"set_topk_percent: a percentage, 0 < k <= 100, got {v}")
+                self.topk_percent.fill_(float(v))
+
     def forward(self, outputs, labels):
+        if not self.has_topk:
+            return self._but_topk(outputs, labels)
+        topk = self.w_topk * ops.topk_ce(outputs, labels, self.topk_percent, per_image=self.topk_per_image,
+                                         ignore_index=self.ignore_index)
+        others = self.has_lovasz or self.has_base or self.dist_weights is not None
+        return self._but_topk(outputs, labels) + topk if others else topk
+
+    def _but_topk(self, outputs, labels):
+        """the total of every name but `topk`"""
         if not self.has_lovasz:
             return self._named(outputs, labels)
         lovasz = self.w_lovasz * ops.lovasz_softmax(outputs, labels, per_image=self.lovasz_per_image, classes=self.lovasz_classes,
@@ -207,7 +267,7 @@ class Criterion(nn.Module):
         return self._named(outputs, labels) + lovasz if self.has_base or self.dist_weights is not None else lovasz
 
     def _named(self, outputs, labels):
-        """the total of every name but `lovasz`"""
+        """the total of every name but `lovasz` and `topk`"""
         if self.dist_weights is None:
             return self._base(outputs, labels)
         dist = ops.dist_loss(outputs, labels, self.dist_weights, surface=self.has_surface, hausdorff=self.has_hausdorff)

@@ -330,5 +330,86 @@ def lovasz_order(errors: Tensor) -> Tensor:
     return perm
 
 
+# =====================================================================================================
+# Top-k cross-entropy (hard-pixel mining, the CE half of nnU-Net's DC_and_topk_loss; csrc/topk_ce.hip; not in the reference)
+# =====================================================================================================
+class TopKCEFn(Function):
+    """The top-k cross-entropy (include/cenet_hip.h spells it out).  Forward: keys, the radix select of the threshold, the tie
+    rank and the weights wgt [B,H,W] fp32, which the backward — one launch — applies.  kpercent is one fp32 on the device, read
+    there.  The workspace comes from the caching allocator and is free again after the forward; nothing synchronises.  The
+    gradient goes to `logits` only."""
+
+    @staticmethod
+    def forward(ctx, logits, target, kpercent, per_image, ignore_index):
+        logits, target = _c(logits), _c(target)
+        B, K, H, W = logits.shape
+        ws = _empty((kern.topk_ce_ws_bytes(B, H, W, per_image) // 4,), logits, torch.int32)
+        wgt = _empty((B, H, W), logits)
+        loss = _empty((1,), logits)
+        kern.topk_ce_fwd(logits, target, kpercent, ws, wgt, loss, B, K, H, W, per_image, ignore_index)
+        ctx.save_for_backward(logits, target, wgt)
+        ctx.ignore_index = ignore_index
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, wgt = ctx.saved_tensors
+        B, K, H, W = logits.shape
+        d = torch.empty_like(logits)
+        kern.topk_ce_bwd(logits, target, wgt, _c(g).reshape(1).float(), d, B, K, H, W, ctx.ignore_index)
+        return d, None, None, None, None
+
+
+_TOPK_PERCENT = {}  # (device, value) -> the value as one fp32 on the device: a Python number is uploaded once per value
+
+
+def _topk_percent(k, ref: Tensor) -> Tensor:
+    if isinstance(k, Tensor):
+        if k.numel() != 1 or k.dtype != torch.float32 or k.device != ref.device:
+            raise ValueError(f"topk_ce: k as a tensor is one fp32 on the logits' device, got {k.dtype} {tuple(k.shape)} on {k.device}")
+        return _c(k).reshape(1)
+    k = float(k)
+    if not 0.0 < k <= 100.0:
+        raise ValueError(f"topk_ce: k is a percentage, 0 < k <= 100, got {k}")
+    buf = _TOPK_PERCENT.get((ref.device, k))
+    if buf is None:
+        buf = _TOPK_PERCENT[(ref.device, k)] = torch.tensor([k], dtype=torch.float32, device=ref.device)
+    return buf
+
+
+def topk_ce(inputs, target, k=10.0, *, per_image=False, ignore_index=None):
+    """The top-k cross-entropy on inputs [B,K,H,W] (fp32 or bf16 logits) and target [B,H,W] (class ids as floats): the mean of the
+    cross-entropy over the k % of the valid pixels with the largest loss, m = max(1, floor(n_valid k / 100)) of them — equal
+    losses by ascending pixel index, so the result is a function of the inputs alone.  k: a Python number (0 < k <= 100, uploaded
+    once per value) or a one-element fp32 tensor on the device, which is read there in place (a schedule can write into it, a
+    captured graph included; the device clamps it into (0, 100]).  per_image: every image on its own, then the mean over the
+    images that have a valid pixel; ignore_index: pixels with that label (and pixels whose label is no class) are in no count and
+    get no gradient.  No valid pixel at all: 0."""
+    if inputs.dim() != 4 or target.shape != (inputs.shape[0],) + tuple(inputs.shape[2:]):
+        raise ValueError(f"topk_ce: inputs [B,K,H,W] and target [B,H,W] expected, got {tuple(inputs.shape)} and "
+                         f"{tuple(target.shape)}")
+    return TopKCEFn.apply(inputs, target.float(), _topk_percent(k, inputs), bool(per_image),
+                          None if ignore_index is None else int(ignore_index))
+
+
+def topk_mask(values: Tensor, m) -> Tensor:
+    """values [S,n] fp32, non-negative; m: an int or S ints (a sequence or an int32 tensor) -> uint8 [S,n], 1 on the m[s] largest
+    values of row s, equal values by ascending index — the selection of topk_ce on its own"""
+    if values.dim() != 2 or values.dtype != torch.float32:
+        raise ValueError(f"topk_mask: values [S,n] fp32 expected, got {values.dtype} {tuple(values.shape)}")
+    S, n = values.shape
+    values = _c(values)
+    if not isinstance(m, Tensor):
+        m = torch.tensor([int(m)] * S if isinstance(m, int) else [int(v) for v in m], dtype=torch.int32)
+    if m.numel() != S:
+        raise ValueError(f"topk_mask: {m.numel()} counts for {S} rows")
+    m = _c(m.to(device=values.device, dtype=torch.int32))
+    ws = _empty((kern.topk_mask_ws_bytes(S, n) // 4,), values, torch.int32)
+    mask = _empty((S, n), values, torch.uint8)
+    kern.topk_mask(values, m, ws, mask, S, n)
+    return mask
+
+
 __all__ = ["DsebCombineFn", "dseb_combine", "DiceCELossFn", "dice_ce_loss", "SegLossExFn", "class_weight_buffer", "seg_loss",
-           "distance_maps", "pred_distance_maps", "DistLossFn", "dist_loss", "LovaszFn", "lovasz_softmax", "lovasz_order"]
+           "distance_maps", "pred_distance_maps", "DistLossFn", "dist_loss", "LovaszFn", "lovasz_softmax", "lovasz_order",
+           "TopKCEFn", "topk_ce", "topk_mask"]

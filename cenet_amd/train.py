@@ -36,10 +36,11 @@ def _as_batches(loader) -> Iterable[dict]:
 
 
 def criterion_args(loss_type: str = "dice,ce", loss_weights: str = "0.5,0.5", dice_class_weights=None, ce_class_weights=None,
-                   ignore_index=None, lovasz_per_image=False) -> argparse.Namespace:
+                   ignore_index=None, lovasz_per_image=False, topk_percent=10.0, topk_per_image=False) -> argparse.Namespace:
     """the `args` train_acdc hands losses.Criterion"""
     return argparse.Namespace(loss_type=loss_type, loss_weights=loss_weights, dice_class_weights=dice_class_weights,
-                              ce_class_weights=ce_class_weights, ignore_index=ignore_index, lovasz_per_image=lovasz_per_image)
+                              ce_class_weights=ce_class_weights, ignore_index=ignore_index, lovasz_per_image=lovasz_per_image,
+                              topk_percent=topk_percent, topk_per_image=topk_per_image)
 
 
 def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, base_lr: float = 0.05, momentum: float = 0.9,
@@ -49,7 +50,8 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
                test_volumes: Optional[Callable[[], Iterable]] = None, save_dir: Optional[str] = None, img_size: int = 224,
                test_resize: str = "device", dice_class_weights=None, ce_class_weights=None, ignore_index=None,
                test_postprocess=None, dist_weight_schedule: Optional[Callable[[int], tuple]] = None, test_tta=None,
-               test_spacing=None, test_nsd_tolerance=None, lovasz_per_image=False) -> dict:
+               test_spacing=None, test_nsd_tolerance=None, lovasz_per_image=False, topk_percent=10.0,
+               topk_per_image=False, topk_schedule: Optional[Callable[[int], float]] = None) -> dict:
     """main_acdc.py:200-290.  tr_loader yields {'image' [B,C,H,W] float (C = the network's input channels), 'label' [B,H,W]} batches (host or device tensors);
     val_batches() yields (image [1,1,H,W], label [1,H,W]) pairs for the per-epoch validation (main_acdc.py:218-231).
     optimizer / scheduler: the reference's --optimizer / --scheduler strings (main_acdc.py:34-35, core.py:12-41); `momentum`
@@ -71,7 +73,11 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
     Criterion.set_dist_weights — the weights are read on the device, so the captured step is replayed, not recaptured
     (Kervadec's rebalancing moves the surface weight every epoch)
     loss_type may name `lovasz` too (the Lovasz-Softmax loss, its weight in loss_weights; lovasz_per_image: every image on its
-    own): sort, ranks and coefficients are launches of the captured step like any other"""
+    own): sort, ranks and coefficients are launches of the captured step like any other
+    loss_type may name `topk` (the top-k cross-entropy, its weight in loss_weights; topk_percent: the k % of pixels with the
+    largest loss that count; topk_per_image: every image on its own); topk_schedule: epoch -> percent, called at the start of
+    every epoch and handed to Criterion.set_topk_percent — the percentage is read on the device, so the captured step is
+    replayed, not recaptured"""
     import os
 
     from . import checkpoint, evaluate
@@ -87,9 +93,12 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
     dev = torch.device(device)
     net = net.to(dev).train()
     crit = losses.Criterion(num_classes, criterion_args(loss_type, loss_weights, dice_class_weights, ce_class_weights,
-                                                        ignore_index, lovasz_per_image)).to(dev)
+                                                        ignore_index, lovasz_per_image, topk_percent=topk_percent,
+                                                        topk_per_image=topk_per_image)).to(dev)
     if dist_weight_schedule is not None and crit.dist_weights is None:
         raise ValueError("dist_weight_schedule: loss_type names neither surface nor hausdorff")
+    if topk_schedule is not None and crit.topk_percent is None:
+        raise ValueError("topk_schedule: loss_type does not name topk")
     arena = optim.ParamArena(net, optim.cenet_segments())
     if optimizer.lower() == "sgd":
         opt = optim.FusedSGD(arena, lr=base_lr, momentum=momentum, weight_decay=weight_decay)
@@ -138,6 +147,8 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
         net.train()
         if dist_weight_schedule is not None:
             crit.set_dist_weights(*dist_weight_schedule(epoch))
+        if topk_schedule is not None:
+            crit.set_topk_percent(topk_schedule(epoch))
         run = torch.zeros((), device=dev)
         n_img = 0
         for batch in DevicePrefetcher(_as_batches(tr_loader), dev):

@@ -716,6 +716,42 @@ int cenet_lovasz_fwd_f32(const float* inputs, const float* labels, void* ws, lon
                          cenet_stream_t stream);
 int cenet_lovasz_bwd_f32(const float* inputs, const float* coef, const float* gout, float* dinputs, int B, int K, int H, int W,
                          int from_probs, cenet_stream_t stream);
+/* Top-k cross-entropy: the mean of the cross-entropy over the k % of pixels with the largest loss (hard-pixel mining, the CE half
+ * of nnU-Net's DC_and_topk_loss; csrc/topk_ce.hip; not in the reference).  logits [B,K,H,W], 2 <= K <= 16; labels [B,H,W] class
+ * ids as floats.  For pixel i, l_i = log sum_c exp(x_c - max) - (x_y - max) in fp32, clamped at >= 0.  The label picks x_y by the
+ * comparison label == (float)c and is never a memory index.  A pixel whose label is ignore_index (has_ignore), or matches no
+ * class, is INVALID: in no count, zero gradient.  A SEGMENT is the whole batch (S = 1, n = B H W) or, with per_image, one image
+ * (S = B, n = H W); n_valid = its valid pixels; m = max(1, floor(n_valid k / 100)) with k = kpercent[0], a float32 percentage READ
+ * ON THE DEVICE and clamped into (0, 100], the product and quotient in double: (long long)((double)n_valid * (double)k / 100.0).
+ * The kept set of a segment is its m valid pixels with the largest l, equal l by ascending pixel index (numpy:
+ * argsort(-l, kind="stable")[:m]).  Segment loss = the mean of l over the kept set; loss = the mean over the S_valid segments
+ * that have a valid pixel; no valid pixel in the batch: loss = 0 exactly, gradient all zeros.  wgt [B,H,W] fp32 = 1 / (m_s S_valid)
+ * on a kept pixel, 0 elsewhere.  Backward, one launch: dlogits_j = gout[0] wgt_i (p_j - [j == y_i]), exact zeros where wgt_i == 0;
+ * dlogits may not be logits.  Non-finite logits are outside the contract (unspecified result, no fault: nothing is indexed by a
+ * value).
+ * Forward: keys (bits of l, + 1; 0 = invalid) as [S, n] uint32 with the first digit histogram and n_valid in the same pass; a
+ * radix SELECT of 4 rounds of 8 bits from the top (a histogram of the digit over the keys whose higher bits equal the prefix so
+ * far — LDS bins per workgroup, integer atomics into the segment's 256 bins: counts only —, then one workgroup a segment picks
+ * the digit at which the count from the top reaches the remaining quota) that leaves the threshold key tau and r, the number of
+ * pixels with key == tau that are kept (no key moves); the tie rank (key == tau per tile of cenet_topk_tile() elements, an
+ * exclusive scan over the tiles, ballots and the lane number inside a tile: no atomic decides an order); kept iff key > tau, or
+ * key == tau and rank < r; one partial sum of the kept l per workgroup stored in ws and a one-workgroup launch that adds them in a
+ * fixed order in double — no float atomics, bitwise reproducible, nothing read back.  ws: ws_bytes >= cenet_topk_ce_ws_bytes(B,
+ * H, W, per_image) bytes of scratch, 4-byte aligned.  CENET_EINVAL (nothing launched) unless 2 <= K <= 16, B, H, W >= 1,
+ * S <= 65535, n < 2^31 and the workspace is large enough.
+ * cenet_topk_mask_f32 is the selection alone: values [S, n] fp32, non-negative; m [S] int32 (device; clamped into [0, n]) ->
+ * mask [S, n] uint8 = 1 on the m[s] largest values of segment s, equal values by ascending index; ws_bytes >=
+ * cenet_topk_mask_ws_bytes(S, n); CENET_EINVAL unless 1 <= S <= 65535 and 1 <= n < 2^31. */
+int cenet_topk_tile(void);
+long cenet_topk_ce_ws_bytes(int B, int H, int W, int per_image);
+long cenet_topk_mask_ws_bytes(int S, int n);
+int cenet_topk_mask_f32(const float* values, const int* m, void* ws, long ws_bytes, unsigned char* mask, int S, int n,
+                        cenet_stream_t stream);
+int cenet_topk_ce_fwd_f32(const float* logits, const float* labels, const float* kpercent, void* ws, long ws_bytes, float* wgt,
+                          float* loss, int B, int K, int H, int W, int per_image, int has_ignore, int ignore_index,
+                          cenet_stream_t stream);
+int cenet_topk_ce_bwd_f32(const float* logits, const float* labels, const float* wgt, const float* gout, float* dlogits, int B,
+                          int K, int H, int W, int has_ignore, int ignore_index, cenet_stream_t stream);
 /* torch.optim.SGD(momentum, weight_decay) over a flat arena; hyper5 (device) = [lr, momentum, wd, grad_scale, first_step] */
 int cenet_sgd_step_f32(float* p, const float* g, float* buf, const float* hyper5, long n, cenet_stream_t stream);
 /* torch.optim.Adam / AdamW (amsgrad off) over a flat arena, one pass; exp_avg / exp_avg_sq are the flat fp32 moment buffers.
@@ -837,6 +873,11 @@ int cenet_lovasz_fwd_bf16(const unsigned short* inputs, const float* labels, voi
     cenet_stream_t stream);
 int cenet_lovasz_bwd_bf16(const unsigned short* inputs, const float* coef, const float* gout, unsigned short* dinputs, int B,
     int K, int H, int W, int from_probs, cenet_stream_t stream);
+/* topk_ce.hip */
+int cenet_topk_ce_fwd_bf16(const unsigned short* logits, const float* labels, const float* kpercent, void* ws, long ws_bytes,
+    float* wgt, float* loss, int B, int K, int H, int W, int per_image, int has_ignore, int ignore_index, cenet_stream_t stream);
+int cenet_topk_ce_bwd_bf16(const unsigned short* logits, const float* labels, const float* wgt, const float* gout,
+    unsigned short* dlogits, int B, int K, int H, int W, int has_ignore, int ignore_index, cenet_stream_t stream);
 /* norm.hip */
 int cenet_layernorm_fwd_bf16(const unsigned short* x, const float* gamma, const float* beta, unsigned short* y, float* mean,
     float* rstd, int rows, int C, float eps, cenet_stream_t stream);
