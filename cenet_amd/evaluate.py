@@ -560,7 +560,8 @@ def _save_case(test_save_path, case, z_spacing, prediction, image, label):
 
 @torch.no_grad()
 def predict_volume(net, volume: torch.Tensor, patch_size: Sequence[int], batch_slices: int = 32, normalize=None,
-                   labels: torch.Tensor = None, tta=None, conf_out: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                   labels: torch.Tensor = None, tta=None, conf_out: torch.Tensor = None, window_overlap=None,
+                   window_importance: str = "gaussian") -> Tuple[torch.Tensor, torch.Tensor]:
     """The prediction loop of test_single_volume (metrics_eval.py:41-58, utils_synapse.py:53-76) without leaving the device:
     volume [D, H, W] on the device -> (prediction [D, H, W] class ids as float, counts [K + 1, 3] int64 over the whole volume
     when `labels` [D, H, W] is given, else None).  Per chunk of `batch_slices` slices: zoom(order=3) to `patch_size` (skipped when
@@ -569,10 +570,16 @@ def predict_volume(net, volume: torch.Tensor, patch_size: Sequence[int], batch_s
     `tta` (a name of TTA_SETS or a tuple of view codes; None: off): a chunk holds max(1, batch_slices // T) slices, whose T views go
     through the network as one batch of at most `batch_slices`; one kernel un-views the logit stacks, averages their softmax, takes
     the argmax and resizes back.  `conf_out` (with `tta` only): a [D, H, W] fp32 tensor on the volume's device that receives the
-    winning class's mean probability.  All sides must be >= 2 then."""
+    winning class's mean probability.  All sides must be >= 2 then.
+    `window_overlap` (None: off, all of the above unchanged; a number in [0, 1)): sliding-window inference, `patch_size` is the
+    window and nothing is resized in either direction (`_predict_volume_sw`); `window_importance`: "gaussian" or "constant".
+    `tta` and `conf_out` (the winner's blended probability) are both allowed then."""
     assert volume.dim() == 3, "volume [D,H,W] expected"
     D, H, W = volume.shape
     PH, PW = int(patch_size[0]), int(patch_size[1])
+    if window_overlap is not None:
+        return _predict_volume_sw(net, volume, (PH, PW), batch_slices, normalize, labels, tta, conf_out, window_overlap,
+                                  window_importance)
     resize = (H != PH or W != PW)
     if resize and not kern.vol_resize_supported(H, W, PH, PW):
         raise ValueError(f"the device resize needs sides >= 2, got {(H, W)} -> {(PH, PW)}")
@@ -653,6 +660,143 @@ def _predict_volume_tta(net, volume, patch, batch_slices, normalize, labels, tta
     return pred, total
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# sliding-window inference at the image's own resolution (csrc/sliding_window.hip): nnU-Net's window grid, MONAI's Gaussian
+# importance map; not in the reference, whose resize recipe stays the default.  Off unless asked for.
+# ---------------------------------------------------------------------------------------------------------------------
+_SW_WEIGHTS = {}  # (P, importance, device) -> the factor on the device: a handful of small vectors, uploaded once each
+
+
+def _window_args(window_overlap, window_importance):
+    """both checked before anything runs"""
+    if isinstance(window_overlap, bool) or not isinstance(window_overlap, (int, float)) or not 0.0 <= window_overlap < 1.0:
+        raise ValueError(f"window_overlap: None or a number in [0, 1) expected, got {window_overlap!r}")
+    if window_importance not in kern.SW_IMPORTANCE:
+        raise ValueError(f"window_importance: one of {kern.SW_IMPORTANCE} expected, got {window_importance!r}")
+
+
+def _sw_device_only(window_overlap, window_importance, resize, on_dev):
+    """the volume wrappers run the sliding window through predict_volume only, as `_tta_device_only`"""
+    if window_overlap is None:
+        return {}
+    _window_args(window_overlap, window_importance)
+    if resize != "device":
+        raise ValueError(f"window_overlap={window_overlap!r} needs resize='device', got resize={resize!r}")
+    if on_dev is None:
+        raise ValueError(f"window_overlap={window_overlap!r}: this case takes the host route (a 2-D input, or an axis of length 1), "
+                         f"which has no sliding-window inference")
+    return dict(window_overlap=window_overlap, window_importance=window_importance)
+
+
+def _sw_weight(P: int, importance: str, device) -> torch.Tensor:
+    key = (P, importance, str(device))
+    if key not in _SW_WEIGHTS:
+        _SW_WEIGHTS[key] = torch.from_numpy(kern.sw_weights(P, importance)).to(device)
+    return _SW_WEIGHTS[key]
+
+
+def _sw_plan(H, W, PH, PW, overlap, importance, tta, device):
+    """(oy, ox, wy, wx, view mask, T): the origin tables (host lists) and the importance map's two factors on `device`"""
+    _window_args(overlap, importance)
+    mask, T = (1, 1) if tta is None else _tta_mask(tta, PH, PW)
+    return (kern.sw_origins(H, PH, overlap), kern.sw_origins(W, PW, overlap), _sw_weight(PH, importance, device),
+            _sw_weight(PW, importance, device), mask, T)
+
+
+def _sw_chunk(net, src, plan, patch, max_batch, normalize, pad_value, labels, pred, conf, semantics=None):
+    """one chunk src [n, C, H, W] of a sliding-window prediction: all windows in one launch, their views in one more, the network
+    in forwards of at most `max_batch` written into ONE logits buffer, one merge launch into pred / conf [n, H, W].  Returns the
+    chunk's counts [K + 1, 3] int32 (None without labels)."""
+    import contextlib
+    oy, ox, wy, wx, mask, T = plan
+    PH, PW = patch
+    n, C, H, W = src.shape
+    nb = n * len(oy) * len(ox)
+    windows = torch.empty((nb, C, PH, PW), device=src.device, dtype=torch.float32)
+    kern.sw_windows(src, windows, oy, ox, n, C, H, W, PH, PW, normalize, pad_value)
+    if T > 1:
+        views = torch.empty((T * nb, C, PH, PW), device=src.device, dtype=torch.float32)
+        kern.tta_views(windows, views, nb, C, PH, PW, mask)
+    else:
+        views = windows
+    with (semantics() if semantics is not None else contextlib.nullcontext()):
+        if T * nb <= max_batch:
+            logits = net(views).contiguous()
+        else:
+            logits = None
+            for s in range(0, T * nb, max_batch):
+                part = net(views[s:s + max_batch])
+                if logits is None:
+                    logits = torch.empty((T * nb,) + tuple(part.shape[1:]), device=part.device, dtype=part.dtype)
+                logits[s:s + max_batch].copy_(part)
+    K = logits.shape[1]
+    counts = None
+    if labels is not None:
+        counts = torch.empty((K + 1, 3), device=src.device, dtype=torch.int32)
+    kern.sw_merge_counts(logits, labels, wy, wx, oy, ox, pred, conf, counts, n, K, PH, PW, H, W, mask)
+    return counts
+
+
+@torch.no_grad()
+def sliding_window_predict(net, images: torch.Tensor, window: Sequence[int], overlap: float = 0.5, importance: str = "gaussian",
+                           tta=None, labels: torch.Tensor = None, batch_windows: int = 32, normalize=None,
+                           pad_value: float = 0.0):
+    """Sliding-window inference of a 2-D batch, the counterpart of `tta_predict`: images [B, C, H, W] -> (pred [B, H, W] class ids
+    as float, conf [B, H, W]: the winner's blended probability, counts [K + 1, 3] int32 as `predict_counts` returns them, or None
+    without `labels`).  The network sees [window] crops at the images' own resolution (origins: `kern.sw_origins`, `overlap` in
+    [0, 1); an image smaller than the window is centred in it and padded with `pad_value`), optionally normalised with
+    `normalize = (mean, std)`; the windows' softmax is blended with the `importance` map ("gaussian" or "constant") and, with
+    `tta`, over its views.  A chunk holds max(1, batch_windows // (windows per image * T)) images; its windows go through `net` in
+    forwards of at most `batch_windows`.  The network's mode and batch semantics are the caller's."""
+    if images.dim() != 4:
+        raise ValueError(f"images [B, C, H, W] expected, got {tuple(images.shape)}")
+    B, C, H, W = images.shape
+    PH, PW = int(window[0]), int(window[1])
+    plan = _sw_plan(H, W, PH, PW, overlap, importance, tta, images.device)
+    batch_windows = max(1, int(batch_windows))
+    chunk = max(1, batch_windows // (len(plan[0]) * len(plan[1]) * plan[5]))
+    images = images.float().contiguous()
+    pred = torch.empty((B, H, W), device=images.device, dtype=torch.float32)
+    conf = torch.empty_like(pred)
+    if labels is not None:
+        labels = labels.reshape(B, H, W).float().contiguous()
+    total = None
+    for s in range(0, B, chunk):
+        counts = _sw_chunk(net, images[s:s + chunk], plan, (PH, PW), batch_windows, normalize, pad_value,
+                           None if labels is None else labels[s:s + chunk], pred[s:s + chunk], conf[s:s + chunk])
+        if counts is not None:
+            total = counts if total is None else total.add_(counts)
+    return pred, conf, total
+
+
+def _predict_volume_sw(net, volume, patch, batch_slices, normalize, labels, tta, conf_out, overlap, importance):
+    """predict_volume with `window_overlap`: per chunk of max(1, batch_slices // (windows per slice * T)) slices the windows, their
+    views, the forwards (at most `batch_slices` windows each, batch-1 semantics: the split cannot change a value) and the fused
+    merge.  The origin tables ride in the kernel arguments and the importance factors are on the device before the loop, which
+    makes no host round trip."""
+    D, H, W = volume.shape
+    PH, PW = patch
+    plan = _sw_plan(H, W, PH, PW, overlap, importance, tta, volume.device)
+    if conf_out is not None and (tuple(conf_out.shape) != (D, H, W) or conf_out.dtype != torch.float32
+                                 or conf_out.device != volume.device or not conf_out.is_contiguous()):
+        raise ValueError(f"conf_out: a contiguous fp32 tensor {(D, H, W)} on {volume.device} expected, got "
+                         f"{tuple(conf_out.shape)} {conf_out.dtype} on {conf_out.device}")
+    batch_slices = max(1, int(batch_slices))
+    chunk = max(1, batch_slices // (len(plan[0]) * len(plan[1]) * plan[5]))
+    volume = volume.float().contiguous()
+    pred = torch.empty((D, H, W), device=volume.device, dtype=torch.float32)
+    total = None
+    if labels is not None:
+        labels = labels.reshape(D, H, W).float().contiguous()
+    for s in range(0, D, chunk):
+        counts = _sw_chunk(net, volume[s:s + chunk].unsqueeze(1), plan, (PH, PW), batch_slices, normalize, 0.0,
+                           None if labels is None else labels[s:s + chunk], pred[s:s + chunk],
+                           None if conf_out is None else conf_out[s:s + chunk], semantics=ops.batch1_semantics)
+        if counts is not None:
+            total = counts.long() if total is None else total + counts.long()
+    return pred, total
+
+
 def _surface_kwargs(spacing, nsd_tolerance, ndim: int) -> dict:
     """what the volume wrappers add to their `label_metrics` call: nothing for (None, None), so that call is then the one it has
     always been; both are checked here, before the network runs"""
@@ -671,7 +815,8 @@ def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int
                        device=None, resize: str = "host", test_save_path=None, case=None,
                        z_spacing: float = 1.0, postprocess=None, lcc_connectivity: int = 1,
                        lcc_per_slice: bool = False, tta=None, spacing=None,
-                       nsd_tolerance=None) -> List[Tuple[float, float, float, float]]:
+                       nsd_tolerance=None, window_overlap=None,
+                       window_importance: str = "gaussian") -> List[Tuple[float, float, float, float]]:
     """test_single_volume (metrics_eval.py:37-84) for a 3-D volume: image / label [1,D,H,W] or [D,H,W] (tensor or ndarray).
     Slices are resized to `patch_size` with scipy's cubic zoom and the predictions back with order 0 exactly as the
     reference does (host side), but the network runs on batches of slices and the metrics on the device.
@@ -684,6 +829,9 @@ def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int
     `spacing`: the volume's voxel spacing, a number or (z, y, x), in which hd95 and assd are then reported (`label_metrics`; None:
     voxels, as the reference).  `z_spacing` is not read for it: it only goes into the side-car file of `test_save_path`.
     `nsd_tolerance`: every tuple gains the normalised surface Dice at that tolerance as its last element.
+    `window_overlap` (None: off; a number in [0, 1)) / `window_importance`: sliding-window inference inside `predict_volume`
+    with `patch_size` windows instead of the two resizes; needs resize="device" like `tta`, and composes with it and with
+    everything after the prediction.
     Returns [(dice, hd95, jaccard, assd)] for classes 1..classes-1."""
     from scipy.ndimage import zoom
     assert resize in ("host", "device"), resize
@@ -693,8 +841,9 @@ def test_single_volume(image, label, net, classes: int, patch_size: Sequence[int
     net.eval()
     on_dev = _device_case(image, label, device, patch_size) if resize == "device" else None
     _tta_device_only(tta, resize, on_dev)
+    sw = _sw_device_only(window_overlap, window_importance, resize, on_dev)
     if on_dev is not None:
-        pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices, tta=tta)
+        pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices, tta=tta, **sw)
         pred_d = _postprocessed(pred_d, classes, postprocess, lcc_connectivity, lcc_per_slice)
         if test_save_path is not None:
             _save_case(test_save_path, case, z_spacing, pred_d, on_dev[0], on_dev[1])
@@ -751,7 +900,7 @@ def synapse_metric_percase(pred: torch.Tensor, gt: torch.Tensor, method: str = "
 def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequence[int] = (256, 256), test_save_path=None,
                                case=None, z_spacing: float = 1.0, batch_slices: int = 32, device=None, resize: str = "host",
                                postprocess=None, lcc_connectivity: int = 1, lcc_per_slice: bool = False, tta=None,
-                               spacing=None, nsd_tolerance=None):
+                               spacing=None, nsd_tolerance=None, window_overlap=None, window_importance: str = "gaussian"):
     """test_single_volume of utils_synapse.py:49-97: every slice of the volume [1, D, H, W] is resized to `patch_size` (cubic
     zoom), normalised with Normalize([0.5], [0.5]) (`ToTensor` leaves float arrays unscaled), classified, and the prediction
     resized back with order 0; returns [(dice, hd95)] for classes 1..classes-1.  A 2-D input takes the reference's second branch
@@ -761,7 +910,9 @@ def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequ
     normalisation inside the resize kernel; the 2-D branch has no resize and is the same in both modes.  `postprocess`,
     `lcc_connectivity`, `lcc_per_slice`, `tta`: as for `test_single_volume` (the 2-D branch takes no `tta`: ValueError).
     `spacing` (a number, or one entry per axis of the input: (z, y, x), or (y, x) for the 2-D branch) and `nsd_tolerance`: as for
-    `test_single_volume`; the tuples are then (dice, hd95 in that unit[, nsd]).  `z_spacing` stays the side-car's alone."""
+    `test_single_volume`; the tuples are then (dice, hd95 in that unit[, nsd]).  `z_spacing` stays the side-car's alone.
+    `window_overlap` / `window_importance`: as for `test_single_volume` (the normalisation is then fused into the window gather;
+    the 2-D branch takes none: ValueError)."""
     from scipy.ndimage import zoom
     assert resize in ("host", "device"), resize
     _check_postprocess(postprocess)
@@ -771,8 +922,9 @@ def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequ
     net.eval()
     on_dev = _device_case(image, label, device, patch_size) if resize == "device" else None
     _tta_device_only(tta, resize, on_dev)
+    sw = _sw_device_only(window_overlap, window_importance, resize, on_dev)
     if on_dev is not None:
-        pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices, normalize=(0.5, 0.5), tta=tta)
+        pred_d, _ = predict_volume(net, on_dev[0], patch_size, batch_slices, normalize=(0.5, 0.5), tta=tta, **sw)
         pred_d = _postprocessed(pred_d, classes, postprocess, lcc_connectivity, lcc_per_slice)
         if test_save_path is not None:
             _save_case(test_save_path, case, z_spacing, pred_d, on_dev[0], on_dev[1])
@@ -811,19 +963,21 @@ def synapse_test_single_volume(image, label, net, classes: int, patch_size: Sequ
 
 @torch.no_grad()
 def val_single_volume(image, label, net, classes: int, patch_size: Sequence[int] = (224, 224), batch_slices: int = 32,
-                      device=None, resize: str = "device", tta=None) -> List[float]:
+                      device=None, resize: str = "device", tta=None, window_overlap=None,
+                      window_importance: str = "gaussian") -> List[float]:
     """val_single_volume (metrics_eval.py:87-122): the prediction of `test_single_volume`, scored with calculate_dice_percase
     only — Dice of classes 1..classes-1 over the whole volume.  `resize="device"`: the overlap counts come out of the argmax +
     resize-back kernel, nothing but those 3 (K + 1) integers leaves the device.  `resize="host"` (and cases the device resize
     does not take): the reference's host resizes, counts from the device.  `tta`: as for `test_single_volume`; the counts then
-    come out of the merge kernel."""
+    come out of the merge kernel.  `window_overlap` / `window_importance`: as for `test_single_volume`."""
     assert resize in ("host", "device"), resize
     device = device or next(net.parameters()).device
     net.eval()
     on_dev = _device_case(image, label, device, patch_size) if resize == "device" else None
     _tta_device_only(tta, resize, on_dev)
+    sw = _sw_device_only(window_overlap, window_importance, resize, on_dev)
     if on_dev is not None:
-        _, counts = predict_volume(net, on_dev[0], patch_size, batch_slices, labels=on_dev[1], tta=tta)
+        _, counts = predict_volume(net, on_dev[0], patch_size, batch_slices, labels=on_dev[1], tta=tta, **sw)
         return class_dice(counts)[:classes - 1]
     image = image.squeeze(0).cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
     label = label.squeeze(0).cpu().numpy() if torch.is_tensor(label) else np.asarray(label)
@@ -843,11 +997,11 @@ def val_single_volume(image, label, net, classes: int, patch_size: Sequence[int]
 def inference(net, volumes, classes: int, patch_size: Sequence[int] = (224, 224), z_spacing: float = 1.0, test_save_path=None,
               log=print, resize: str = "device", batch_slices: int = 32, device=None, postprocess=None,
               lcc_connectivity: int = 1, lcc_per_slice: bool = False, tta=None, spacing=None,
-              nsd_tolerance=None) -> Tuple[float, float]:
+              nsd_tolerance=None, window_overlap=None, window_importance: str = "gaussian") -> Tuple[float, float]:
     """inference (utils_acdc.py:7-33): `test_single_volume` for every case of `volumes` (the test loader's dicts: `image`
     [1, D, H, W], `label`, `case_name` — a string or the DataLoader's one-element list), the reference's per-case and per-class
     log lines through `log`, and (mean dice, mean hd95): the metric table averaged over the cases, then over the classes.
-    `postprocess`, `lcc_connectivity`, `lcc_per_slice` and `tta` go to `test_single_volume`.
+    `postprocess`, `lcc_connectivity`, `lcc_per_slice`, `tta` and `window_overlap` / `window_importance` go to `test_single_volume`.
     `spacing`: the voxel spacing hd95 and assd are reported in — a number or (z, y, x) for all cases, or one per case: a dict
     {case_name: spacing}, which must hold every case, or a list with one spacing per case in the order of `volumes` (a list of
     three NUMBERS is one spacing for all cases).  `nsd_tolerance`: the tables gain the normalised surface Dice as a fifth column,
@@ -861,6 +1015,9 @@ def inference(net, volumes, classes: int, patch_size: Sequence[int] = (224, 224)
                                                lcc_per_slice=lcc_per_slice)
     if tta is not None:
         post["tta"] = tta
+    if window_overlap is not None:
+        _window_args(window_overlap, window_importance)
+        post.update(window_overlap=window_overlap, window_importance=window_importance)
     if nsd_tolerance is not None:
         post["nsd_tolerance"] = nsd_tolerance
     net.eval()
@@ -906,32 +1063,44 @@ def _binary_dc(result: torch.Tensor, reference: torch.Tensor) -> float:
     return 2.0 * int((a & b).sum()) / float(sa + sb) if (sa + sb) else 0.0
 
 
+def _skin_predict(net, img, tta, window, window_overlap):
+    """the class map of one skin batch: the plain argmax, `tta_predict`, or with `window` (the network's input size; `window_overlap`
+    defaults to 0.5) `sliding_window_predict`, which takes `tta` along"""
+    if window is None:
+        if window_overlap is not None:
+            raise ValueError(f"window_overlap={window_overlap!r} needs `window`, the network's input size")
+        return predict_counts(net(img))[0] if tta is None else tta_predict(net, img, tta)[0]
+    return sliding_window_predict(net, img, window, 0.5 if window_overlap is None else window_overlap, tta=tta)[0]
+
+
 @torch.no_grad()
-def skin_val(net, vl_loader, device=None, tta=None) -> float:
+def skin_val(net, vl_loader, device=None, tta=None, window=None, window_overlap=None) -> float:
     """val of utils_skin.py:97-113: mean over the loader's batches of dc(argmax(softmax(logits), 1).squeeze(0), label batch).
-    `tta`: the prediction of `tta_predict` instead of the plain argmax."""
+    `tta`: the prediction of `tta_predict` instead of the plain argmax.  `window` (and `window_overlap`, 0.5 when None): the
+    prediction of `sliding_window_predict` at the images' own size."""
     device = device or next(net.parameters()).device
     net.eval()
     dc_sum, n = 0.0, 0
     for batch in vl_loader:
         img, lab = batch["image"].to(device), batch["label"].to(device)
-        pred = predict_counts(net(img.float()))[0] if tta is None else tta_predict(net, img.float(), tta)[0]
+        pred = _skin_predict(net, img.float(), tta, window, window_overlap)
         dc_sum += _binary_dc(pred.squeeze(0), lab)
         n += 1
     return dc_sum / max(n, 1)
 
 
 @torch.no_grad()
-def skin_test(net, te_loader, device=None, tta=None) -> Tuple[float, float, float]:
+def skin_test(net, te_loader, device=None, tta=None, window=None, window_overlap=None) -> Tuple[float, float, float]:
     """test of utils_skin.py:131-170 (batch size 1, as the reference's test loader): (mean dice, pixel accuracy, mean IoU) with
     the ground truth read as `label[0, 0]` and calc_iou(pd > 0.5, gt > 0.5) = |A & B| / |A or B| (0.0 for an empty union,
-    utils_skin.py:13-27).  `tta`: the prediction of `tta_predict` instead of the plain argmax."""
+    utils_skin.py:13-27).  `tta`: the prediction of `tta_predict` instead of the plain argmax; `window` / `window_overlap`: as for
+    `skin_val`."""
     device = device or next(net.parameters()).device
     net.eval()
     dc_sum, correct, total, ious, n = 0.0, 0, 0, [], 0
     for batch in te_loader:
         img, lab = batch["image"].float().to(device), batch["label"].float().to(device)
-        pred = predict_counts(net(img))[0] if tta is None else tta_predict(net, img, tta)[0]
+        pred = _skin_predict(net, img, tta, window, window_overlap)
         pd = pred.squeeze(0)
         gt = lab[0, 0]
         correct += int((pd == gt).sum())

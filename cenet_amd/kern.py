@@ -1612,6 +1612,78 @@ def tta_argmax_resize_counts(logits, labels, pred, conf, counts, n, K, PH, PW, H
     _call("cenet_tta_argmax_resize_counts_f32", logits, labels, pred, conf, counts, n, K, PH, PW, H, W, view_mask)
 
 
+# sliding-window inference (sliding_window.hip): the window grid is nnU-Net's, the Gaussian importance map MONAI's (sigma_scale 0.125)
+SW_MAX_WINDOWS = 32  # per axis (SW_MAXW)
+SW_IMPORTANCE = ("gaussian", "constant")
+
+
+def sw_origins(L: int, P: int, overlap: float):
+    """the window origins along an axis of length L for windows of side P: one centred window (origin -((P - L) // 2), the rest
+    is padding) for L <= P, else N = ceil((L - P) / (P (1 - overlap))) + 1 windows at round(i (L - P) / (N - 1))"""
+    import numpy as np
+    L, P = int(L), int(P)
+    if L < 1 or P < 1:
+        raise ValueError(f"sliding window: sides >= 1 expected, got image side {L}, window side {P}")
+    if isinstance(overlap, bool) or not isinstance(overlap, (int, float)) or not 0.0 <= overlap < 1.0:
+        raise ValueError(f"window overlap: a number in [0, 1) expected, got {overlap!r}")
+    if L <= P:
+        return [-((P - L) // 2)]
+    N = int(math.ceil((L - P) / (P * (1.0 - overlap)))) + 1
+    if N > SW_MAX_WINDOWS:
+        raise ValueError(f"sliding window: {N} windows of side {P} along an axis of {L} at overlap {overlap}, at most "
+                         f"{SW_MAX_WINDOWS} are supported")
+    o = [int(np.round(i * (L - P) / (N - 1))) for i in range(N)]
+    if any(b <= a for a, b in zip(o, o[1:])):  # (a step below one pixel: P (1 - overlap) < 1)
+        raise ValueError(f"sliding window: overlap {overlap} of a window of side {P} steps by less than a pixel")
+    return o
+
+
+def sw_weights(P: int, importance: str = "gaussian"):
+    """one factor [P] of the separable importance map as a float32 numpy vector, computed in float64: "gaussian"
+    exp(-0.5 ((i - (P - 1) / 2) / (0.125 P))^2), "constant" ones"""
+    import numpy as np
+    if importance not in SW_IMPORTANCE:
+        raise ValueError(f"window importance: one of {SW_IMPORTANCE} expected, got {importance!r}")
+    if importance == "constant":
+        return np.ones(int(P), dtype=np.float32)
+    i = np.arange(int(P), dtype=np.float64)
+    return np.exp(-0.5 * ((i - (P - 1) / 2.0) / (0.125 * P)) ** 2).astype(np.float32)
+
+
+def _sw_table(o):
+    """an origin table as the C int array the entry points read on the host"""
+    import numpy as np
+    return np.ascontiguousarray(np.asarray(o, dtype=np.int64).astype(np.int32).reshape(-1))
+
+
+def sw_windows(src, out, oy, ox, n, C, H, W, PH, PW, normalize=None, pad_value=0.0):
+    """cenet_sw_windows_f32 (sliding_window.hip): src [n, C, H, W] fp32 -> out [n * len(oy) * len(ox), C, PH, PW], window
+    (b, iy, ix) holding source pixel (oy[iy] + y, ox[ix] + x), `pad_value` outside the slice; normalize = (mean, std) or None.
+    oy / ox: sequences of ints (host); the library checks them"""
+    ty, tx = _sw_table(oy), _sw_table(ox)
+    assert src.is_contiguous() and out.is_contiguous()
+    assert src.numel() == n * C * H * W and out.numel() == n * ty.size * tx.size * C * PH * PW
+    mean, std = normalize if normalize is not None else (0.0, 1.0)
+    _launch("cenet_sw_windows_f32", src, out, ty.ctypes.data, tx.ctypes.data, n, C, H, W, PH, PW, ty.size, tx.size,
+            normalize is not None, mean, std, pad_value)
+
+
+def sw_merge_counts(logits, labels, wy, wx, oy, ox, pred, conf, counts, n, K, PH, PW, H, W, view_mask=1):
+    """cenet_sw_merge_counts (sliding_window.hip): logits [T, n * len(oy) * len(ox), K, PH, PW] fp32 / bf16, one stack per view ->
+    pred [n, H, W] class ids as float (softmax per window and view, blended with wy [PH] x wx [PW] fp32 on the device, argmax) and
+    conf [n, H, W] (or None), the winner's blended probability; labels / counts as for argmax_resize_counts"""
+    ty, tx = _sw_table(oy), _sw_table(ox)
+    assert logits.is_contiguous() and pred.is_contiguous() and wy.is_contiguous() and wx.is_contiguous()
+    assert logits.numel() == _tta_views_of(view_mask) * n * ty.size * tx.size * K * PH * PW and pred.numel() == n * H * W
+    assert wy.numel() == PH and wx.numel() == PW
+    assert conf is None or (conf.is_contiguous() and conf.numel() == n * H * W)
+    if labels is not None:
+        assert labels.is_contiguous() and labels.numel() == n * H * W
+        assert counts is None or counts.numel() == (K + 1) * 3
+    _call("cenet_sw_merge_counts_f32", logits, labels, wy, wx, ty.ctypes.data, tx.ctypes.data, pred, conf, counts, n, K, PH, PW, H,
+          W, ty.size, tx.size, view_mask)
+
+
 def layernorm_fwd_acc(acc, bias, xpre, gamma, beta, y, mean, rstd, rows, Cn, eps):
     """cenet_layernorm_fwd_acc_bf16: LayerNorm straight from a split-K fp32 accumulator (+ bias); acc is zero afterwards"""
     _launch("cenet_layernorm_fwd_acc_bf16", acc, bias, xpre, gamma, beta, y, mean, rstd, rows, Cn, eps)

@@ -51,7 +51,8 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
                test_resize: str = "device", dice_class_weights=None, ce_class_weights=None, ignore_index=None,
                test_postprocess=None, dist_weight_schedule: Optional[Callable[[int], tuple]] = None, test_tta=None,
                test_spacing=None, test_nsd_tolerance=None, lovasz_per_image=False, topk_percent=10.0,
-               topk_per_image=False, topk_schedule: Optional[Callable[[int], float]] = None) -> dict:
+               topk_per_image=False, topk_schedule: Optional[Callable[[int], float]] = None,
+               test_window_overlap=None) -> dict:
     """main_acdc.py:200-290.  tr_loader yields {'image' [B,C,H,W] float (C = the network's input channels), 'label' [B,H,W]} batches (host or device tensors);
     val_batches() yields (image [1,1,H,W], label [1,H,W]) pairs for the per-epoch validation (main_acdc.py:218-231).
     optimizer / scheduler: the reference's --optimizer / --scheduler strings (main_acdc.py:34-35, core.py:12-41); `momentum`
@@ -59,7 +60,8 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
     test_volumes() yields the test loader's dicts (`image` [1,D,H,W], `label`, `case_name`) and needs val_batches: after an
     epoch whose validation Dice is >= the best so far, evaluate.inference runs over them (slices resized to img_size, `test_resize`
     as evaluate.test_single_volume takes it, `test_postprocess` as its `postprocess`: None or "lcc", `test_tta` as its `tta`: None, a name of evaluate.TTA_SETS or a tuple of view codes,
-    with test_resize="device" only, `test_spacing` / `test_nsd_tolerance` as its `spacing` / `nsd_tolerance`: the voxel spacing in
+    with test_resize="device" only, `test_window_overlap` as its `window_overlap`: None or a number in [0, 1) for sliding-window
+    inference with img_size windows, with test_resize="device" only, `test_spacing` / `test_nsd_tolerance` as its `spacing` / `nsd_tolerance`: the voxel spacing in
     which te_HD95 is then reported, for all cases or per case, and the tolerance of the normalised surface Dice, which adds
     'test_nsd' to the result); only when its Dice is >= the best test Dice do BOTH bests move and `best.pth` is
     written (main_acdc.py:272-278: a validation gain without a test gain moves neither); the last epoch writes
@@ -88,6 +90,10 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
         evaluate._tta_mask(test_tta, img_size, img_size)
         if test_resize != "device":
             raise ValueError(f"test_tta={test_tta!r} needs test_resize='device', got {test_resize!r}")
+    if test_window_overlap is not None:
+        evaluate._window_args(test_window_overlap, "gaussian")
+        if test_resize != "device":
+            raise ValueError(f"test_window_overlap={test_window_overlap!r} needs test_resize='device', got {test_resize!r}")
     if save_dir is not None and test_volumes is None:
         raise ValueError("save_dir: the checkpoints of main_acdc.py:272-289 are written by the test inference, pass test_volumes")
     dev = torch.device(device)
@@ -177,6 +183,7 @@ def train_acdc(net, tr_loader, *, num_classes: int = 4, max_epochs: int = 1, bas
                                     resize=test_resize,
                                     **({} if test_postprocess is None else {"postprocess": test_postprocess}),
                                     **({} if test_tta is None else {"tta": test_tta}),
+                                    **({} if test_window_overlap is None else {"window_overlap": test_window_overlap}),
                                     **({} if test_spacing is None else {"spacing": test_spacing}),
                                     **({} if test_nsd_tolerance is None else {"nsd_tolerance": test_nsd_tolerance}))
             te_dice, te_hd = te[:2]

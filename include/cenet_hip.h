@@ -1266,6 +1266,35 @@ int cenet_tta_argmax_resize_counts_bf16(const unsigned short* logits, const floa
                                         unsigned* counts, int n, int K, int PH, int PW, int H, int W, int view_mask,
                                         cenet_stream_t stream);
 
+/* Sliding-window inference at the image's own resolution (sliding_window.hip): the network runs on overlapping [PH, PW] windows of
+ * a [H, W] slice, the windows' class probabilities are blended with a separable importance map, nothing is resized.
+ * oy_host [nwy] / ox_host [nwx]: the window origins per axis, in HOST memory; window (b, iy, ix) is entry (b * nwy + iy) * nwx + ix
+ * of the window batch and holds source pixel (oy[iy] + y, ox[ix] + x) at (y, x).  An origin may be negative (a slice smaller
+ * than the window).  Both tables are checked before anything is launched and reach the kernels by value in the kernel
+ * arguments (no upload, no synchronisation): strictly ascending, first <= 0, o[i + 1] <= o[i] + P, last + P >= L, 1..32 entries,
+ * every window on the slice (o[0] > -P, last < L) — so every output pixel lies in a window.
+ * cenet_sw_windows_f32: src [n, C, H, W] -> out [n * nwy * nwx, C, PH, PW], all windows in one launch: a bit copy inside the
+ * slice, or with normalize != 0 the fp32 (x - mean) / std (a true division); pad_value, stored as given, outside.
+ * cenet_sw_merge_counts_*: logits [T, n * nwy * nwx, K, PH, PW], stack t computed from view t (cenet_tta_views_f32, view_mask
+ * and T as there; 0x01: no augmentation) of the window batch -> pred [n, H, W] (class ids as floats).  Per output pixel (y, x):
+ * every window that covers it in ascending (iy, ix), inside a window every view in ascending code: the K logits at the pixel's
+ * place in that view become a max-subtracted fp32 softmax p and sum[k] += w * p[k]; once per window wsum += w, with w = wy[y - oy[iy]] *
+ * wx[x - ox[ix]] (wy [PH], wx [PW]: the importance map's two fp32 factors, on the device, positive).  pred is the first maximum
+ * of the sums under `>`, conf (or NULL) [n, H, W] = sum[pred] / (wsum * T).  The order of the additions is fixed: two calls
+ * agree to the bit.  A window's padding is never read.  labels / counts as for cenet_argmax_resize_counts_*.  Non-finite
+ * logits are not special-cased: a NaN sum never wins under `>`.
+ * CENET_EINVAL (nothing launched) for a null src / out / logits / pred / wy / wx / table, labels without counts, n or C < 1, a
+ * side < 1, K outside 1..16, a view_mask outside 1..255, a transposed view with PH != PW, a table that fails the checks above or
+ * a plane of more than 2^31 - 1 pixels. */
+int cenet_sw_windows_f32(const float* src, float* out, const int* oy_host, const int* ox_host, int n, int C, int H, int W, int PH,
+                         int PW, int nwy, int nwx, int normalize, float mean, float std, float pad_value, cenet_stream_t stream);
+int cenet_sw_merge_counts_f32(const float* logits, const float* labels, const float* wy, const float* wx, const int* oy_host,
+                              const int* ox_host, float* pred, float* conf, unsigned* counts, int n, int K, int PH, int PW, int H,
+                              int W, int nwy, int nwx, int view_mask, cenet_stream_t stream);
+int cenet_sw_merge_counts_bf16(const unsigned short* logits, const float* labels, const float* wy, const float* wx,
+                               const int* oy_host, const int* ox_host, float* pred, float* conf, unsigned* counts, int n, int K,
+                               int PH, int PW, int H, int W, int nwy, int nwx, int view_mask, cenet_stream_t stream);
+
 /* LayerNorm of a split-K accumulator (norm.hip, round 5; pvtv2.py:93-95,99-100: sr conv -> norm): acc [rows, C] fp32 holds the
  * conv's products (zero-at-rest accumulator of a split-K GEMM); xpre = bf16(acc + bias) (the rows the LayerNorm backward reads),
  * y = LayerNorm(xpre) * gamma + beta, mean / rstd [rows]; acc is left zero.  bias may be NULL.  C % 4 == 0, C <= 512. */

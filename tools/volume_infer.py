@@ -15,6 +15,8 @@ blob labels, under the parent's per-class `metric_percase(method="pairs")` loop,
 behind `evaluate.AUTO_PAIRS_PER_BOX_VOXEL`: two overlapping balls of growing radius under both methods.  Prints one JSON line.
 --tta NAME adds a third mode, `device_tta`: resize="device" with that view set of evaluate.TTA_SETS (its split has `tta_views`, and
 `resize_back` is the fused merge).
+--window-overlap X adds the mode `device_window`: resize="device" with sliding-window inference (PATCH windows at the volume's own
+resolution, no resize; its split has `sw_windows` and `sw_merge`), with the view set of --tta when that is given.
 --spacing Z Y X scores in that voxel spacing (hd95 / assd in its unit, the fp64 kernels of csrc/edt.hip), --nsd TAU adds the
 normalised surface Dice at that tolerance.  With --spacing, --report is the SPACED report instead (`spaced_report`, written to
 --report-out as well, profiles/volume_metrics_spacing.json): per volume the spaced transform and the spaced `label_metrics` beside
@@ -76,32 +78,34 @@ class Parts:
 SURFACE = {}  # spacing= / nsd_tolerance= of --spacing / --nsd, handed to test_single_volume
 
 
-def call(net, image, label, mode, dev, tta=None):
+def call(net, image, label, mode, dev, tta=None, window_overlap=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     m = evaluate.test_single_volume(image, label, net, K, patch_size=PATCH, batch_slices=32, device=dev, resize=mode, tta=tta,
-                                    **SURFACE)
+                                    **({} if window_overlap is None else {"window_overlap": window_overlap}), **SURFACE)
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3, m
 
 
-def split_call(net, image, label, mode, dev, tta=None):
+def split_call(net, image, label, mode, dev, tta=None, window_overlap=None):
     """one call with every part wrapped; the wrappers are taken off again"""
     p = Parts()
     saved = (scipy.ndimage.zoom, kern.vol_resize_cubic, kern.argmax_resize_counts, evaluate.label_metrics, net.forward,
-             kern.tta_views, kern.tta_argmax_resize_counts)
+             kern.tta_views, kern.tta_argmax_resize_counts, kern.sw_windows, kern.sw_merge_counts)
     kern.tta_views = p.wrap("tta_views", saved[5])
     kern.tta_argmax_resize_counts = p.wrap("resize_back", saved[6])
+    kern.sw_windows = p.wrap("sw_windows", saved[7])
+    kern.sw_merge_counts = p.wrap("sw_merge", saved[8])
     scipy.ndimage.zoom = p.wrap(lambda *a, **k: "resize_in" if k.get("order", 3) == 3 else "resize_back", saved[0])
     kern.vol_resize_cubic = p.wrap("resize_in", saved[1])
     kern.argmax_resize_counts = p.wrap("resize_back", saved[2])
     evaluate.label_metrics = p.wrap("metrics", saved[3])
     net.forward = p.wrap("forward", saved[4])
     try:
-        total, _ = call(net, image, label, mode, dev, tta)
+        total, _ = call(net, image, label, mode, dev, tta, window_overlap)
     finally:
         scipy.ndimage.zoom, kern.vol_resize_cubic, kern.argmax_resize_counts, evaluate.label_metrics = saved[:4]
-        kern.tta_views, kern.tta_argmax_resize_counts = saved[5:]
+        kern.tta_views, kern.tta_argmax_resize_counts, kern.sw_windows, kern.sw_merge_counts = saved[5:]
         del net.forward
     p.t["other"] = total - sum(p.t.values())
     p.t["total"] = total
@@ -281,6 +285,9 @@ def main():
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--tta", choices=sorted(evaluate.TTA_SETS), default=None,
                     help="also time resize='device' with this test-time augmentation set (entry `device_tta`)")
+    ap.add_argument("--window-overlap", type=float, default=None,
+                    help="also time resize='device' with sliding-window inference at this overlap in [0, 1) (entry `device_window`; "
+                         "it takes --tta along)")
     ap.add_argument("--spacing", type=float, nargs=3, metavar=("Z", "Y", "X"), default=None,
                     help="voxel spacing: hd95 / assd in its unit; with --report: the spaced report")
     ap.add_argument("--nsd", type=float, default=None, help="tolerance of the normalised surface Dice (the unit of --spacing)")
@@ -300,7 +307,7 @@ def main():
     net = net.to(dev).eval()
     kern.set_compute_bf16(args.bf16)
     res = {"tool": "volume_infer", "device": torch.cuda.get_device_name(0), "kernel_src_sha16": build.source_sha16(),
-           "precision": "bf16" if args.bf16 else "fp32", "patch": list(PATCH), "batch_slices": 32, "unit": "ms", "metrics_method": args.metrics, "tta": args.tta,
+           "precision": "bf16" if args.bf16 else "fp32", "patch": list(PATCH), "batch_slices": 32, "unit": "ms", "metrics_method": args.metrics, "tta": args.tta, "window_overlap": args.window_overlap,
            "spacing": args.spacing, "nsd_tolerance": args.nsd, "volumes": {}}
     real_metric = evaluate.label_metrics
     for name, shape in VOLUMES.items():
@@ -318,16 +325,19 @@ def main():
             evaluate.label_metrics = lambda p, g, k, kind="acdc", method=None, **kw: [(0.0,) * (5 if args.nsd else 4)] * (k - 1)
         entry = {"shape": list(shape), "max_border_pairs": pairs, "metrics_timed": timed_metrics}
         preds = {}
-        for mode, tta in [("host", None), ("device", None)] + ([("device_tta", args.tta)] if args.tta else []):
+        modes = [("host", None, None), ("device", None, None)] + ([("device_tta", args.tta, None)] if args.tta else []) + \
+            ([("device_window", args.tta, args.window_overlap)] if args.window_overlap is not None else [])
+        for mode, tta, wov in modes:
             how = mode.split("_")[0]
-            call(net, image, label, how, dev, tta)  # warm-up
-            runs = [call(net, image, label, how, dev, tta)[0] for _ in range(5)]
-            splits = [split_call(net, image, label, how, dev, tta) for _ in range(3)]
+            call(net, image, label, how, dev, tta, wov)  # warm-up
+            runs = [call(net, image, label, how, dev, tta, wov)[0] for _ in range(5)]
+            splits = [split_call(net, image, label, how, dev, tta, wov) for _ in range(3)]
             keys = sorted(set().union(*splits))
             entry[mode] = {"total_runs": [round(v, 3) for v in runs], "total_median": round(statistics.median(runs), 3),
                            "total_spread": round(max(runs) - min(runs), 3),
                            "split_median": {k: round(statistics.median(s.get(k, 0.0) for s in splits), 3) for k in keys}}
-            preds[mode] = evaluate.val_single_volume(image, label, net, K, patch_size=PATCH, device=dev, resize=how, tta=tta)
+            preds[mode] = evaluate.val_single_volume(image, label, net, K, patch_size=PATCH, device=dev, resize=how, tta=tta,
+                                                     window_overlap=wov)
         evaluate.label_metrics = real_metric
         entry["speedup"] = round(entry["host"]["total_median"] / entry["device"]["total_median"], 3)
         entry["class_dice"] = {m: [round(v, 6) for v in preds[m]] for m in preds}
