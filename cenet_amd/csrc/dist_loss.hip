@@ -8,19 +8,18 @@
 // w: two floats in DEVICE memory, read by every launch (a graph replay sees what was last written there).  A term that is not
 // present is left out, not multiplied by 0; without the Hausdorff term d2p is never read.  The maps are constants: no gradient
 // flows through the threshold.
-// STORE-AND-SUM as seg_loss_ex.hip: workgroup g of the forward stores its two partial sums as row g of the workspace, a
+// STORE-AND-SUM (loss_pixel.h): workgroup g of the forward stores its two partial sums as row g of the workspace, a
 // one-workgroup launch adds the rows in a fixed order in double.  No float atomics: loss and gradient are bitwise reproducible.
 // Backward, one launch: a_j = w[0] phi_j + 2 w[1] (p_j - g_j)(d2g_j + d2p_j), a_0 = 0;  dlogit_j = gout p_j (a_j - sum_c p_c a_c) / N.
-#include "common.h"
+#include "loss_pixel.h"
 #include "../../include/cenet_hip.h"
 
-#define DL_MAXK 16
 enum { DL_SURFACE = 1, DL_HAUSDORFF = 2 };
 
 static inline int dl_fwd_it(int K) { return K > 9 ? 4 : 8; }  // pixels per thread of the forward kernel
 static inline long dl_rows(int B, int K, long HW) { return (long)cdiv(HW, 256 * dl_fwd_it(K)) * B; }
 static inline bool dl_shape_ok(int B, int K, int H, int W) {
-  return B > 0 && B <= 65535 && K >= 2 && K <= DL_MAXK && H >= 1 && W >= 1 && (long)H * W <= 0x7fffffffL - 256 * 8;
+  return B > 0 && B <= 65535 && K >= 2 && K <= PX_MAXK && H >= 1 && W >= 1 && (long)H * W <= 0x7fffffffL - 256 * 8;
 }
 
 extern "C" long cenet_dist_loss_ws_floats(int B, int K, int H, int W) {
@@ -28,25 +27,6 @@ extern "C" long cenet_dist_loss_ws_floats(int B, int K, int H, int W) {
   return 2 * dl_rows(B, K, (long)H * W);
 }
 
-// softmax of one pixel's K logits, in place
-template <int KM>
-__device__ __forceinline__ void dl_softmax(float* v, int K) {
-  float mx = -3.4e38f;
-#pragma unroll
-  for (int c = 0; c < KM; ++c)
-    if (c < K) mx = fmaxf(mx, v[c]);
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < KM; ++c)
-    if (c < K) {
-      v[c] = fast_exp(v[c] - mx);
-      s += v[c];
-    }
-  const float inv = fast_rcp(s);
-#pragma unroll
-  for (int c = 0; c < KM; ++c)
-    if (c < K) v[c] *= inv;
-}
 __device__ __forceinline__ float dl_phi(int d2g, bool inside) {
   const float d = sqrtf((float)d2g);
   return inside ? 1.f - d : d;
@@ -66,7 +46,7 @@ __global__ __launch_bounds__(256) void dl_fwd_kernel(const T* __restrict__ logit
   const float* lab = labels + (long)b * HW;
   const int* g0 = d2g + (long)b * (K - 1) * HW;
   const int* p0 = hd ? d2p + (long)b * (K - 1) * HW : nullptr;
-  float ssum = 0.f, hsum = 0.f;
+  float sum[2] = {0.f, 0.f};  // surface, Hausdorff
 #pragma unroll 2
   for (int k = 0; k < IT; ++k) {
     const int p = (blockIdx.x * IT + k) * 256 + threadIdx.x;
@@ -74,54 +54,37 @@ __global__ __launch_bounds__(256) void dl_fwd_kernel(const T* __restrict__ logit
     float v[KM];
     int dg[KM], dp[KM];
 #pragma unroll
-    for (int c = 0; c < KM; ++c)
+    for (int c = 0; c < KM; ++c)  // (class by class, a logit between its two maps)
       if (c < K) {
         v[c] = ldf(lb0 + (long)c * HW + p);
         dg[c] = c ? g0[(long)(c - 1) * HW + p] : 0;
         dp[c] = (c && hd) ? p0[(long)(c - 1) * HW + p] : 0;
       }
     const float t = lab[p];
-    dl_softmax<KM>(v, K);
+    px_softmax<KM, false>(v, K);
 #pragma unroll
     for (int c = 1; c < KM; ++c)
       if (c < K) {
         const bool in = t == (float)c;
-        if (surf) ssum += v[c] * dl_phi(dg[c], in);
+        if (surf) sum[0] += v[c] * dl_phi(dg[c], in);
         if (hd) {
           const float e = v[c] - (in ? 1.f : 0.f);
-          hsum += e * e * ((float)dg[c] + (float)dp[c]);
+          sum[1] += e * e * ((float)dg[c] + (float)dp[c]);
         }
       }
   }
-  // wave sums -> LDS -> the four waves added in a fixed order -> this workgroup's row
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  ssum = wave_sum(ssum);
-  hsum = wave_sum(hsum);
-  if (lane == 0) wred[wave][0] = ssum, wred[wave][1] = hsum;
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    const int j = threadIdx.x;
-    rows[((long)blockIdx.y * gridDim.x + blockIdx.x) * 2 + j] = (wred[0][j] + wred[1][j]) + (wred[2][j] + wred[3][j]);
-  }
+  block_store_row(sum, wred, rows + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 2);
 }
 
-// one workgroup of 1024 threads: thread t adds rows t, t + 1024, ... of both values in double, then a tree over the threads
 __global__ __launch_bounds__(1024) void dl_finalize_kernel(const float* __restrict__ rows, const float* __restrict__ w,
                                                           float* __restrict__ loss, long nrows, double inv_n, int flags) {
   __shared__ double acc[2][1024];
-  const int t = threadIdx.x;
-  double s = 0.0, h = 0.0;
-  for (long r = t; r < nrows; r += 1024) s += (double)rows[2 * r], h += (double)rows[2 * r + 1];
-  acc[0][t] = s, acc[1][t] = h;
-  __syncthreads();
-  for (int off = 512; off > 0; off >>= 1) {
-    if (t < off) acc[0][t] += acc[0][t + off], acc[1][t] += acc[1][t + off];
-    __syncthreads();
-  }
-  if (t == 0) {
+  double sum[2];  // surface, Hausdorff
+  rows_sum_f64(acc, nrows, [&](long r, int j) { return (double)rows[2 * r + j]; }, sum);
+  if (threadIdx.x == 0) {
     double l = 0.0;
-    if (flags & DL_SURFACE) l += (double)w[0] * acc[0][0] * inv_n;
-    if (flags & DL_HAUSDORFF) l += (double)w[1] * acc[1][0] * inv_n;
+    if (flags & DL_SURFACE) l += (double)w[0] * sum[0] * inv_n;
+    if (flags & DL_HAUSDORFF) l += (double)w[1] * sum[1] * inv_n;
     loss[0] = (float)l;
   }
 }
@@ -147,14 +110,14 @@ __global__ __launch_bounds__(256) void dl_bwd_kernel(const T* __restrict__ logit
     float v[KM], a[KM];
     int dg[KM], dp[KM];
 #pragma unroll
-    for (int c = 0; c < KM; ++c)
+    for (int c = 0; c < KM; ++c)  // (class by class, a logit between its two maps)
       if (c < K) {
         v[c] = ldf(lb0 + (long)c * HW + p);
         dg[c] = c ? g0[(long)(c - 1) * HW + p] : 0;
         dp[c] = (c && hd) ? p0[(long)(c - 1) * HW + p] : 0;
       }
     const float t = lab[p];
-    dl_softmax<KM>(v, K);
+    px_softmax<KM, false>(v, K);
     float dot = 0.f;
     a[0] = 0.f;
 #pragma unroll
@@ -189,9 +152,7 @@ static int dist_loss_fwd_impl(const T* logits, const float* labels, const int* d
   if (!ws || !loss || ws_floats < cenet_dist_loss_ws_floats(B, K, H, W)) return CENET_EINVAL;
   const int HW = H * W, flags = (surface ? DL_SURFACE : 0) | (hausdorff ? DL_HAUSDORFF : 0);
   const dim3 blocks(cdiv(HW, 256 * dl_fwd_it(K)), B);
-  if (K <= 4) CENET_LAUNCH((dl_fwd_kernel<T, 4>), blocks, dim3(256), stream, logits, labels, d2g, d2p, ws, K, HW, flags);
-  else if (K <= 9) CENET_LAUNCH((dl_fwd_kernel<T, 9>), blocks, dim3(256), stream, logits, labels, d2g, d2p, ws, K, HW, flags);
-  else CENET_LAUNCH((dl_fwd_kernel<T, DL_MAXK>), blocks, dim3(256), stream, logits, labels, d2g, d2p, ws, K, HW, flags);
+  CENET_LAUNCH_KM(dl_fwd_kernel, T, K, blocks, dim3(256), stream, logits, labels, d2g, d2p, ws, K, HW, flags);
   CENET_CHECK_LAUNCH();
   const double inv_n = 1.0 / ((double)B * (K - 1) * HW);
   CENET_LAUNCH(dl_finalize_kernel, dim3(1), dim3(1024), stream, (const float*)ws, w, loss, dl_rows(B, K, HW), inv_n, flags);
@@ -212,9 +173,7 @@ static int dist_loss_bwd_impl(const T* logits, const float* labels, const int* d
   const int HW = H * W, flags = (surface ? DL_SURFACE : 0) | (hausdorff ? DL_HAUSDORFF : 0);
   const dim3 blocks(cdiv(HW, 256 * 4), B);
   const float inv_n = (float)(1.0 / ((double)B * (K - 1) * HW));
-  if (K <= 4) CENET_LAUNCH((dl_bwd_kernel<T, 4>), blocks, dim3(256), stream, logits, labels, d2g, d2p, w, gout, dlogits, K, HW, inv_n, flags);
-  else if (K <= 9) CENET_LAUNCH((dl_bwd_kernel<T, 9>), blocks, dim3(256), stream, logits, labels, d2g, d2p, w, gout, dlogits, K, HW, inv_n, flags);
-  else CENET_LAUNCH((dl_bwd_kernel<T, DL_MAXK>), blocks, dim3(256), stream, logits, labels, d2g, d2p, w, gout, dlogits, K, HW, inv_n, flags);
+  CENET_LAUNCH_KM(dl_bwd_kernel, T, K, blocks, dim3(256), stream, logits, labels, d2g, d2p, w, gout, dlogits, K, HW, inv_n, flags);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
 }

@@ -3,10 +3,11 @@
 //   SGD(momentum 0.9, weight decay)           utils/core.py:19-21 (torch.optim.SGD semantics)
 // The loss never leaves the device: per-class Dice sums (over the WHOLE batch, as the reference does) and the CE sum
 // are reduced with block partials + float atomics into a small accumulator that the backward kernel re-reads.
-#include "common.h"
+#include "loss_pixel.h"
 #include "../../include/cenet_hip.h"
 
 #define LOSS_MAXK 16
+static_assert(LOSS_MAXK == PX_MAXK, "CENET_LAUNCH_KM launches the widest kernels as <T, PX_MAXK>");
 // float atomics onto one cache line serialise (~12 ns each), so thousands of workgroups must not share a line.
 // Round 5: one value PER 64-BYTE LINE — replica s of value v sits at acc[(v * ns + s) * 16], ns = loss_ns(K) replicas.  With the
 // 13 - 65 values of a replica in one line (the layout until then), the ~10 000 adds of a forward launch queued on 16 lines: 26 of the
@@ -259,9 +260,7 @@ static int seg_loss_fwd_impl(const T* logits, const float* labels, float* acc, f
   if (B > 65535) return CENET_EUNSUPPORTED;
   const dim3 blocks(cdiv(HW, 256 * (K > 9 ? 4 : DICE_IT)), B);
   const int bnd = (int)(w_bd != 0.f);
-  if (K <= 4) CENET_LAUNCH((dice_ce_fwd_kernel<T, 4>), blocks, dim3(256), stream, logits, labels, acc, K, HW, npix, W, bnd);
-  else if (K <= 9) CENET_LAUNCH((dice_ce_fwd_kernel<T, 9>), blocks, dim3(256), stream, logits, labels, acc, K, HW, npix, W, bnd);
-  else CENET_LAUNCH((dice_ce_fwd_kernel<T, LOSS_MAXK>), blocks, dim3(256), stream, logits, labels, acc, K, HW, npix, W, bnd);
+  CENET_LAUNCH_KM(dice_ce_fwd_kernel, T, K, blocks, dim3(256), stream, logits, labels, acc, K, HW, npix, W, bnd);
   CENET_LAUNCH(dice_ce_finalize_kernel, dim3(1), dim3(128), stream, acc, loss, K, (float)npix, w_dice, w_ce, w_bd);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
@@ -278,9 +277,7 @@ static int seg_loss_bwd_impl(const T* logits, const float* labels, const float* 
   const long npix = (long)B * HW;
   if (B > 65535) return CENET_EUNSUPPORTED;
   const dim3 blocks(cdiv(HW, 256 * 4), B);
-  if (K <= 4) CENET_LAUNCH((dice_ce_bwd_kernel<T, 4>), blocks, dim3(256), stream, logits, labels, acc, gout, dlogits, K, HW, npix, w_dice, w_ce, w_bd);
-  else if (K <= 9) CENET_LAUNCH((dice_ce_bwd_kernel<T, 9>), blocks, dim3(256), stream, logits, labels, acc, gout, dlogits, K, HW, npix, w_dice, w_ce, w_bd);
-  else CENET_LAUNCH((dice_ce_bwd_kernel<T, LOSS_MAXK>), blocks, dim3(256), stream, logits, labels, acc, gout, dlogits, K, HW, npix, w_dice, w_ce, w_bd);
+  CENET_LAUNCH_KM(dice_ce_bwd_kernel, T, K, blocks, dim3(256), stream, logits, labels, acc, gout, dlogits, K, HW, npix, w_dice, w_ce, w_bd);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
 }

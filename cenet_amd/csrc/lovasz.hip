@@ -10,46 +10,25 @@
 //   keys     one pass over inputs and labels: fp32 softmax, key = bits(e) + 1 (non-negative floats order as their bits; key 0 =
 //            ignored pixel, which therefore sorts below every other), payload = pixel index << 1 | g
 //   4 x (hist, rowscan, scatter)   stable LSD radix sort of the S segments, 8 bits a pass over all 32 key bits, DESCENDING (the
-//            digit is taken from the inverted key).  hist: digit counts per tile of LV_TILE elements (integer LDS atomics: counts
-//            only).  rowscan: exclusive scan of every (segment, digit) row over its tiles (a group of lanes a row).  scatter:
+//            digit is taken from the inverted key).  hist: digit counts per tile of TILE_ELEMS elements (integer LDS atomics: counts
+//            only).  rowscan (tile_rank.h's tile_rowscan_kernel): exclusive scan of every (segment, digit) row over its tiles (a
+//            group of lanes a row).  scatter:
 //            the element's place = digits below it in the segment + the same digit in earlier tiles + the same digit earlier in
 //            this tile.  The last is a RANK, and no atomic decides it: a wave takes its items in order, finds the lanes holding the
 //            same digit with eight ballots, and ranks by lane number; waves are ordered by a fixed walk over their counts.  The
 //            tile is put in digit order in LDS first, so that the stores of a digit's run are contiguous.
-//   gcount, rowscan   g bits per tile of the sorted order, scanned over the tiles: F before every tile, and G as the row total
-//   coef     F_i by ballots inside the tile, the increment in double from the integers, a = dL/dp scattered to coef [B,K,H,W], one
-//            partial sum of e_(i) (J_i - J_{i-1}) / divisor per workgroup STORED as a row
-//   finalize one workgroup adds the rows in a fixed order in double (the pattern of seg_loss_ex.hip / dist_loss.hip)
+//   gcount, rowscan   (tile_count_kernel<lv_is_g>, tile_rowscan_kernel) g bits per tile of the sorted order, scanned over the
+//            tiles: F before every tile, and G as the row total
+//   coef     F_i by ballots inside the tile (tile_rank), the increment in double from the integers, a = dL/dp scattered to coef
+//            [B,K,H,W], one partial sum of e_(i) (J_i - J_{i-1}) / divisor per workgroup STORED as a row (block_store_row)
+//   finalize one workgroup adds the rows in a fixed order in double (loss_pixel.h's rows_sum_f64)
 // No float atomics anywhere: loss, coef and gradient have the same bits on every run.
-#include "common.h"
-#include "wave_ballot.h"
-#include "../../include/cenet_hip.h"
+#include "loss_pixel.h"
+#include "tile_rank.h"
 
-#define LV_MAXK 16
-#define LV_IT 8
-#define LV_TILE (256 * LV_IT)
 #define LV_BINS 256
 #define LV_PASSES 4
 enum { LV_IGNORE = 1, LV_PROBS = 2 };
-typedef unsigned long long lv_mask_t;
-
-template <int KM>
-__device__ __forceinline__ void lv_softmax(float* v, int K) {
-  float mx = -3.4e38f;
-#pragma unroll
-  for (int c = 0; c < KM; ++c)
-    if (c < K) mx = fmaxf(mx, v[c]);
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < KM; ++c)
-    if (c < K) {
-      v[c] = expf(v[c] - mx);  // libm's, not v_exp_f32: the order of near-equal errors follows the probabilities' last bits
-      s += v[c];
-    }
-#pragma unroll
-  for (int c = 0; c < KM; ++c)
-    if (c < K) v[c] = v[c] / s;
-}
 
 // ---- keys -------------------------------------------------------------------------------------------------------------------------
 // grid (gx * B), gx = ceil(HW / 1024): block -> image b = blockIdx.x / gx; a thread owns 4 pixels, consecutive lanes on
@@ -66,11 +45,9 @@ __global__ __launch_bounds__(256) void lv_keys_kernel(const T* __restrict__ in, 
     const int p = (bx * 4 + k) * 256 + threadIdx.x;
     if (p >= HW) continue;
     float v[KM];
-#pragma unroll
-    for (int c = 0; c < KM; ++c)
-      if (c < K) v[c] = ldf(in0 + (long)c * HW + p);
+    px_load<KM>(v, in0, HW, p, K);
     const float t = lab[p];
-    if (!(flags & LV_PROBS)) lv_softmax<KM>(v, K);
+    if (!(flags & LV_PROBS)) px_softmax<KM, true>(v, K);
     const bool ign = (flags & LV_IGNORE) && (int)t == ignore_index;
     const unsigned i = per_image ? (unsigned)p : (unsigned)b * (unsigned)HW + (unsigned)p;
 #pragma unroll
@@ -79,7 +56,7 @@ __global__ __launch_bounds__(256) void lv_keys_kernel(const T* __restrict__ in, 
         const bool g = !ign && t == (float)c;
         const float e = fabsf((g ? 1.f : 0.f) - v[c]);
         const long at = (long)(per_image ? b * K + c : c) * n + i;
-        keys[at] = ign ? 0u : __float_as_uint(e) + 1u;
+        keys[at] = tile_key(e, !ign);
         pay[at] = (i << 1) | (g ? 1u : 0u);
       }
   }
@@ -89,7 +66,7 @@ __global__ __launch_bounds__(256) void lv_keys_kernel(const T* __restrict__ in, 
 __global__ __launch_bounds__(256) void lv_order_keys_kernel(const float* __restrict__ e, unsigned* __restrict__ keys,
                                                            unsigned* __restrict__ pay, long total, int n) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    keys[i] = __float_as_uint(e[i]) + 1u;
+    keys[i] = tile_key(e[i], true);
     pay[i] = (unsigned)(i % n) << 1;
   }
 }
@@ -109,59 +86,23 @@ __global__ __launch_bounds__(256) void lv_hist_kernel(const unsigned* __restrict
   __syncthreads();
   const unsigned* k0 = keys + (long)s * n;
 #pragma unroll
-  for (int k = 0; k < LV_IT; ++k) {
-    const unsigned i = (unsigned)tile * LV_TILE + k * 256 + threadIdx.x;
+  for (int k = 0; k < TILE_IT; ++k) {
+    const unsigned i = (unsigned)tile * TILE_ELEMS + k * 256 + threadIdx.x;
     if (i < (unsigned)n) atomicAdd(&hist[lv_digit(k0[i], shift)], 1u);
   }
   __syncthreads();
   counts[((long)s * LV_BINS + threadIdx.x) * T + tile] = (int)hist[threadIdx.x];
 }
 
-// Exclusive scan of every row data[r T .. r T + T) in place, totals[r] = the row's sum.  A group of Wd lanes (a power of two <= 64,
-// the host picks the smallest that covers T) walks its row 4 Wd values at a time, four consecutive values a lane; 256 / Wd rows per
-// workgroup, grid ceil(rows Wd / 256).
-__global__ __launch_bounds__(256) void lv_rowscan_kernel(int* __restrict__ data, int* __restrict__ totals, long rows, int T, int Wd) {
-  const long r = ((long)blockIdx.x * 256 + threadIdx.x) / Wd;
-  const int gl = threadIdx.x & (Wd - 1);
-  const bool live = r < rows;
-  int* row = data + (live ? r : 0) * T;
-  int carry = 0;
-  for (int base = 0; base < T; base += 4 * Wd) {  // (the same trip count for every thread: the shuffles stay convergent)
-    const int i0 = base + 4 * gl;
-    int v[4], tot = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) tot += v[q] = (live && i0 + q < T) ? row[i0 + q] : 0;
-    int inc = tot;
-    for (int o = 1; o < Wd; o <<= 1) {
-      const int t = __shfl(inc, gl >= o ? gl - o : gl, Wd);
-      if (gl >= o) inc += t;
-    }
-    int at = carry + inc - tot;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (live && i0 + q < T) row[i0 + q] = at;
-      at += v[q];
-    }
-    carry += __shfl(inc, Wd - 1, Wd);
-  }
-  if (live && gl == 0) totals[r] = carry;
-}
-static inline int lv_scan_width(int T) {
-  int w = 1;
-  while (4 * w < T && w < 64) w <<= 1;
-  return w;
-}
-static inline dim3 lv_scan_grid(long rows, int Wd) { return dim3(cdiv(rows * Wd, 256)); }
-
 // grid (T, S).  Wave w owns elements [w 64 IT, (w + 1) 64 IT) of the tile, item k of lane l is element w 64 IT + 64 k + l: the order
-// of the elements is (wave, item, lane), loads are coalesced.  counts: scanned by lv_rowscan_kernel; totals: the row totals.
+// of the elements is (wave, item, lane), loads are coalesced.  counts: scanned by tile_rowscan_kernel; totals: the row totals.
 __global__ __launch_bounds__(256) void lv_scatter_kernel(const unsigned* __restrict__ kin, const unsigned* __restrict__ pin,
                                                         unsigned* __restrict__ kout, unsigned* __restrict__ pout,
                                                         const int* __restrict__ counts, const int* __restrict__ totals, int n, int T,
                                                         int shift) {
   __shared__ int wcnt_s[4][LV_BINS];
   __shared__ int wsum[4], wsum2[4], gdelta[LV_BINS];
-  __shared__ unsigned skey[LV_TILE], spay[LV_TILE];
+  __shared__ unsigned skey[TILE_ELEMS], spay[TILE_ELEMS];
   // wcnt[w] is touched by wave w alone until the barrier behind the ranking loop.  Inside a wave no barrier is needed between
   // the leader's update at item k and another lane's read at item k + 1: the 64 lanes run one instruction stream, a wave's LDS
   // operations complete in issue order, and `volatile` keeps the compiler from caching or reordering the accesses.
@@ -169,7 +110,7 @@ __global__ __launch_bounds__(256) void lv_scatter_kernel(const unsigned* __restr
   const int tile = blockIdx.x, s = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // thread t = digit t: elements of the segment with a smaller digit, plus this digit's in earlier tiles
   const int tot = totals[s * LV_BINS + threadIdx.x];
-  const int inc = lv_wave_incl_scan(tot);
+  const int inc = wave_incl_scan(tot);
   if (lane == 63) wsum[wave] = inc;
 #pragma unroll
   for (int w = 0; w < 4; ++w) wcnt[w][threadIdx.x] = 0;
@@ -179,37 +120,37 @@ __global__ __launch_bounds__(256) void lv_scatter_kernel(const unsigned* __restr
 
   const unsigned* k0 = kin + (long)s * n;
   const unsigned* p0 = pin + (long)s * n;
-  const unsigned start = (unsigned)tile * LV_TILE + wave * (64 * LV_IT) + lane;
-  const lv_mask_t below = ((lv_mask_t)1 << lane) - 1;
-  unsigned key[LV_IT], pv[LV_IT];
-  int loc[LV_IT];
+  const unsigned start = (unsigned)tile * TILE_ELEMS + wave * (64 * TILE_IT) + lane;
+  const wave_mask_t below = ((wave_mask_t)1 << lane) - 1;
+  unsigned key[TILE_IT], pv[TILE_IT];
+  int loc[TILE_IT];
 #pragma unroll
-  for (int k = 0; k < LV_IT; ++k) {
+  for (int k = 0; k < TILE_IT; ++k) {
     const unsigned i = start + 64 * k;
     const bool valid = i < (unsigned)n;
     key[k] = valid ? k0[i] : 0u;
     pv[k] = valid ? p0[i] : 0u;
   }
 #pragma unroll
-  for (int k = 0; k < LV_IT; ++k) {
+  for (int k = 0; k < TILE_IT; ++k) {
     const bool valid = start + 64 * k < (unsigned)n;
     const unsigned d = lv_digit(key[k], shift);
-    lv_mask_t m = lv_ballot(valid);
+    wave_mask_t m = wave_ballot(valid);
 #pragma unroll
     for (int b = 0; b < 8; ++b) {
       const bool bit = (d >> b) & 1;
-      const lv_mask_t bal = lv_ballot(bit);
+      const wave_mask_t bal = wave_ballot(bit);
       m &= bit ? bal : ~bal;
     }
-    if (!valid) m = (lv_mask_t)1 << lane;  // m: the valid lanes of this item with this lane's digit (this lane among them)
+    if (!valid) m = (wave_mask_t)1 << lane;  // m: the valid lanes of this item with this lane's digit (this lane among them)
     const int leader = __builtin_ctzll(m);
     int pre = 0;
     if (valid && lane == leader) {
       pre = wcnt[wave][d];
-      wcnt[wave][d] = pre + lv_popc(m);
+      wcnt[wave][d] = pre + wave_popc(m);
     }
     pre = __shfl(pre, leader);
-    loc[k] = pre + lv_popc(m & below);  // elements of this wave with this digit before this one
+    loc[k] = pre + wave_popc(m & below);  // elements of this wave with this digit before this one
   }
   __syncthreads();
   // thread t = digit t: the tile sorted by digit is laid out in LDS first — tstart = the tile's elements with a smaller digit,
@@ -217,7 +158,7 @@ __global__ __launch_bounds__(256) void lv_scatter_kernel(const unsigned* __restr
   int c[4], ttot = 0;
 #pragma unroll
   for (int w = 0; w < 4; ++w) ttot += c[w] = wcnt[w][threadIdx.x];
-  const int tinc = lv_wave_incl_scan(ttot);
+  const int tinc = wave_incl_scan(ttot);
   if (lane == 63) wsum2[wave] = tinc;
   __syncthreads();
   int run = tinc - ttot;
@@ -230,7 +171,7 @@ __global__ __launch_bounds__(256) void lv_scatter_kernel(const unsigned* __restr
   }
   __syncthreads();
 #pragma unroll
-  for (int k = 0; k < LV_IT; ++k) {
+  for (int k = 0; k < TILE_IT; ++k) {
     if (start + 64 * k >= (unsigned)n) continue;
     const int pos = wcnt[wave][lv_digit(key[k], shift)] + loc[k];
     skey[pos] = key[k];
@@ -240,10 +181,10 @@ __global__ __launch_bounds__(256) void lv_scatter_kernel(const unsigned* __restr
   // consecutive threads take consecutive places of the sorted tile: the stores of a digit's run are contiguous
   unsigned* ko = kout + (long)s * n;
   unsigned* po = pout + (long)s * n;
-  const unsigned left = (unsigned)n - (unsigned)tile * LV_TILE;
-  const int count = left < LV_TILE ? (int)left : LV_TILE;
+  const unsigned left = (unsigned)n - (unsigned)tile * TILE_ELEMS;
+  const int count = left < TILE_ELEMS ? (int)left : TILE_ELEMS;
 #pragma unroll
-  for (int k = 0; k < LV_IT; ++k) {
+  for (int k = 0; k < TILE_IT; ++k) {
     const int j = k * 256 + threadIdx.x;
     if (j >= count) continue;
     const unsigned kv = skey[j];
@@ -256,21 +197,11 @@ __global__ __launch_bounds__(256) void lv_scatter_kernel(const unsigned* __restr
 }
 
 // ---- ranks to coefficients ---------------------------------------------------------------------------------------------------------
-// grid (T, S): gcnt[s T + tile] = pixels of the class (g bit) in the tile of the sorted order
-__global__ __launch_bounds__(256) void lv_gcount_kernel(const unsigned* __restrict__ pay, int* __restrict__ gcnt, int n, int T) {
-  __shared__ int wtot[4];
-  const int tile = blockIdx.x, s = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const unsigned* p0 = pay + (long)s * n;
-  int cnt = 0;
-#pragma unroll
-  for (int k = 0; k < LV_IT; ++k) {
-    const unsigned i = (unsigned)tile * LV_TILE + k * 256 + threadIdx.x;
-    cnt += lv_popc(lv_ballot(i < (unsigned)n && (p0[i] & 1u)));
-  }
-  if (lane == 0) wtot[wave] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) gcnt[(long)s * T + tile] = (wtot[0] + wtot[1]) + (wtot[2] + wtot[3]);
-}
+// the g bit of a payload, for tile_count_kernel: gcnt[s T + tile] = pixels of the class in the tile of the sorted order
+struct lv_is_g {
+  __device__ unsigned seg(int) const { return 0u; }
+  __device__ bool operator()(unsigned pay, unsigned) const { return pay & 1u; }
+};
 
 // grid (T, S), elements as in lv_scatter_kernel.  fbase: gcnt scanned (g bits before the tile); G: the row totals.
 __global__ __launch_bounds__(256) void lv_coef_kernel(const unsigned* __restrict__ keys, const unsigned* __restrict__ pay,
@@ -278,7 +209,7 @@ __global__ __launch_bounds__(256) void lv_coef_kernel(const unsigned* __restrict
                                                      float* __restrict__ coef, float* __restrict__ rows, int n, int T, int B, int K,
                                                      int HW, int per_image, int classes_all) {
   __shared__ int wtot[4];
-  __shared__ float wred[4];
+  __shared__ float wred[4][1];
   const int tile = blockIdx.x, s = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // 1 / divisor of this segment: the mean over the classes that count, with per_image then over the images
   const int Gs = G[s];
@@ -293,28 +224,20 @@ __global__ __launch_bounds__(256) void lv_coef_kernel(const unsigned* __restrict
   }
   const unsigned* k0 = keys + (long)s * n;
   const unsigned* p0 = pay + (long)s * n;
-  const unsigned start = (unsigned)tile * LV_TILE + wave * (64 * LV_IT) + lane;
-  const lv_mask_t upto = (((lv_mask_t)1 << lane) - 1) | ((lv_mask_t)1 << lane);
-  unsigned key[LV_IT], pv[LV_IT];
-  int incl[LV_IT];
-  int run = 0;
+  const unsigned start = (unsigned)tile * TILE_ELEMS + wave * (64 * TILE_IT) + lane;
+  unsigned key[TILE_IT], pv[TILE_IT];
+  int incl[TILE_IT];
 #pragma unroll
-  for (int k = 0; k < LV_IT; ++k) {
+  for (int k = 0; k < TILE_IT; ++k) {
     const unsigned i = start + 64 * k;
     const bool in = i < (unsigned)n;
     key[k] = in ? k0[i] : 0u;
     pv[k] = in ? p0[i] : 0u;
-    const lv_mask_t bal = lv_ballot(key[k] != 0u && (pv[k] & 1u));
-    incl[k] = run + lv_popc(bal & upto);
-    run += lv_popc(bal);
   }
-  if (lane == 0) wtot[wave] = run;
-  __syncthreads();
-  int Fb = fbase[(long)s * T + tile];
-  for (int w = 0; w < wave; ++w) Fb += wtot[w];
-  float acc = 0.f;
+  const int Fb = fbase[(long)s * T + tile] + tile_rank<true>([&](int k) { return key[k] != 0u && (pv[k] & 1u); }, incl, wtot);
+  float acc[1] = {0.f};
 #pragma unroll
-  for (int k = 0; k < LV_IT; ++k) {
+  for (int k = 0; k < TILE_IT; ++k) {
     const unsigned i = start + 64 * k;
     if (i >= (unsigned)n) continue;
     const bool g = pv[k] & 1u;
@@ -323,7 +246,7 @@ __global__ __launch_bounds__(256) void lv_coef_kernel(const unsigned* __restrict
       const long F = (long)Fb + incl[k], Z = (long)i + 1 - F, U = Gs + Z, I = Gs - F;
       const double inc = g ? 1.0 / (double)U : (U == 1 ? 1.0 : (double)I / ((double)U * (double)(U - 1)));
       const float w = (float)(inc * scale);
-      acc += __uint_as_float(key[k] - 1u) * w;
+      acc[0] += tile_key_value(key[k]) * w;
       a = key[k] == 1u ? 0.f : (g ? -w : w);  // e == 0: the gradient of |.| at 0 is 0
     }
     const unsigned pix = pv[k] >> 1;
@@ -336,25 +259,14 @@ __global__ __launch_bounds__(256) void lv_coef_kernel(const unsigned* __restrict
     }
     coef[at] = a;
   }
-  acc = wave_sum(acc);
-  if (lane == 0) wred[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) rows[(long)s * T + tile] = (wred[0] + wred[1]) + (wred[2] + wred[3]);
+  block_store_row(acc, wred, rows + (long)s * T + tile);
 }
 
-// one workgroup of 1024 threads: thread t adds rows t, t + 1024, ... in double, then a tree over the threads
 __global__ __launch_bounds__(1024) void lv_finalize_kernel(const float* __restrict__ rows, float* __restrict__ loss, long nrows) {
-  __shared__ double acc[1024];
-  const int t = threadIdx.x;
-  double s = 0.0;
-  for (long r = t; r < nrows; r += 1024) s += (double)rows[r];
-  acc[t] = s;
-  __syncthreads();
-  for (int off = 512; off > 0; off >>= 1) {
-    if (t < off) acc[t] += acc[t + off];
-    __syncthreads();
-  }
-  if (t == 0) loss[0] = (float)acc[0];
+  __shared__ double acc[1][1024];
+  double sum[1];
+  rows_sum_f64(acc, nrows, [&](long r, int) { return (double)rows[r]; }, sum);
+  if (threadIdx.x == 0) loss[0] = (float)sum[0];
 }
 
 // ---- backward ----------------------------------------------------------------------------------------------------------------------
@@ -374,14 +286,14 @@ __global__ __launch_bounds__(256) void lv_bwd_kernel(const T* __restrict__ in, c
     if (p >= HW) continue;
     float v[KM], a[KM];
 #pragma unroll
-    for (int c = 0; c < KM; ++c)
+    for (int c = 0; c < KM; ++c)  // (class by class, a coefficient beside its input)
       if (c < K) {
         a[c] = a0[(long)c * HW + p];
         if (!probs) v[c] = ldf(in0 + (long)c * HW + p);
       }
     float dot = 0.f;
     if (!probs) {
-      lv_softmax<KM>(v, K);
+      px_softmax<KM, true>(v, K);
 #pragma unroll
       for (int c = 0; c < KM; ++c)
         if (c < K) dot += v[c] * a[c];
@@ -393,7 +305,7 @@ __global__ __launch_bounds__(256) void lv_bwd_kernel(const T* __restrict__ in, c
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
-extern "C" int cenet_lovasz_tile(void) { return LV_TILE; }
+extern "C" int cenet_lovasz_tile(void) { return TILE_ELEMS; }
 
 // the workspace, in 4-byte words: keys and payloads twice (the passes alternate), the digit counts [S, 256, T] and their row totals
 // [S, 256], the g counts [S, T] and their totals G [S], the loss rows [S, T]
@@ -404,7 +316,7 @@ struct lv_ws_t {
   long words;
 };
 static lv_ws_t lv_layout(void* ws, long S, long n) {
-  const long T = cdiv(n, LV_TILE), sn = S * n;
+  const long T = cdiv(n, TILE_ELEMS), sn = S * n;
   unsigned* w = (unsigned*)ws;
   lv_ws_t L;
   L.kA = w, L.pA = w + sn, L.kB = w + 2 * sn, L.pB = w + 3 * sn;
@@ -417,18 +329,12 @@ static lv_ws_t lv_layout(void* ws, long S, long n) {
   L.words = at;
   return L;
 }
-static inline bool lv_seg_ok(long S, long n) { return S >= 1 && S <= 65535 && n >= 1 && n < (1L << 31); }
-static inline bool lv_shape_ok(int B, int K, int H, int W, int per_image, long* S, long* n) {
-  if (B < 1 || K < 2 || K > LV_MAXK || H < 1 || W < 1) return false;
-  const long HW = (long)H * W;
-  if (HW >= (1L << 31)) return false;
-  *S = per_image ? (long)B * K : K;
-  *n = per_image ? HW : HW * B;
-  return lv_seg_ok(*S, *n);
+static inline bool lv_shape_ok(int B, int K, int H, int W, int per_image, long* S, long* n) {  // a segment a class
+  return K >= 2 && K <= PX_MAXK && tile_seg_shape_ok(B, H, W, per_image, K, S, n);
 }
 
 extern "C" long cenet_lovasz_order_ws_bytes(int S, int n) {
-  if (!lv_seg_ok(S, n)) return 0;
+  if (!tile_seg_ok(S, n)) return 0;
   return 4 * lv_layout(nullptr, S, n).words;
 }
 extern "C" long cenet_lovasz_ws_bytes(int B, int K, int H, int W, int per_image) {
@@ -439,14 +345,14 @@ extern "C" long cenet_lovasz_ws_bytes(int B, int K, int H, int W, int per_image)
 
 // keys / payloads in (kA, pA) -> sorted, in (kA, pA) again after the four passes
 static int lv_sort(const lv_ws_t& L, int S, int n, hipStream_t stream) {
-  const int T = cdiv(n, LV_TILE), Wd = lv_scan_width(T);
+  const int T = cdiv(n, TILE_ELEMS);
   unsigned *ki = L.kA, *pi = L.pA, *ko = L.kB, *po = L.pB;
   for (int pass = 0; pass < LV_PASSES; ++pass) {
     const int shift = 8 * pass;
     CENET_LAUNCH(lv_hist_kernel, dim3(T, S), dim3(256), stream, (const unsigned*)ki, L.counts, n, T, shift);
     CENET_CHECK_LAUNCH();
-    CENET_LAUNCH(lv_rowscan_kernel, lv_scan_grid((long)S * LV_BINS, Wd), dim3(256), stream, L.counts, L.totals, (long)S * LV_BINS, T, Wd);
-    CENET_CHECK_LAUNCH();
+    const int rc = tile_rowscan(L.counts, L.totals, (long)S * LV_BINS, T, stream);
+    if (rc != CENET_OK) return rc;
     CENET_LAUNCH(lv_scatter_kernel, dim3(T, S), dim3(256), stream, (const unsigned*)ki, (const unsigned*)pi, ko, po,
                  (const int*)L.counts, (const int*)L.totals, n, T, shift);
     CENET_CHECK_LAUNCH();
@@ -458,7 +364,7 @@ static int lv_sort(const lv_ws_t& L, int S, int n, hipStream_t stream) {
 }
 
 extern "C" int cenet_lovasz_order_f32(const float* errors, void* ws, long ws_bytes, int* perm, int S, int n, hipStream_t stream) {
-  if (!lv_seg_ok(S, n) || !errors || !ws || !perm || ws_bytes < cenet_lovasz_order_ws_bytes(S, n)) return CENET_EINVAL;
+  if (!tile_seg_ok(S, n) || !errors || !ws || !perm || ws_bytes < cenet_lovasz_order_ws_bytes(S, n)) return CENET_EINVAL;
   const lv_ws_t L = lv_layout(ws, S, n);
   const long total = (long)S * n;
   const int blocks = (int)(cdiv(total, 256) < 4096 ? cdiv(total, 256) : 4096);
@@ -478,21 +384,19 @@ static int lovasz_fwd_impl(const T* inputs, const float* labels, void* ws, long 
   long Sl, nl;
   if (!lv_shape_ok(B, K, H, W, per_image, &Sl, &nl)) return CENET_EINVAL;
   if (!inputs || !labels || !ws || !coef || !loss || ws_bytes < cenet_lovasz_ws_bytes(B, K, H, W, per_image)) return CENET_EINVAL;
-  const int S = (int)Sl, n = (int)nl, HW = H * W, Tn = cdiv(n, LV_TILE), gx = cdiv(HW, 1024);
+  const int S = (int)Sl, n = (int)nl, HW = H * W, Tn = cdiv(n, TILE_ELEMS), gx = cdiv(HW, 1024);
   if ((long)gx * B >= (1L << 31)) return CENET_EINVAL;
   const lv_ws_t L = lv_layout(ws, S, n);
   const int flags = (has_ignore ? LV_IGNORE : 0) | (from_probs ? LV_PROBS : 0);
   const dim3 pg(gx * B);
-  if (K <= 4) CENET_LAUNCH((lv_keys_kernel<T, 4>), pg, dim3(256), stream, inputs, labels, L.kA, L.pA, K, HW, gx, nl, per_image, flags, ignore_index);
-  else if (K <= 9) CENET_LAUNCH((lv_keys_kernel<T, 9>), pg, dim3(256), stream, inputs, labels, L.kA, L.pA, K, HW, gx, nl, per_image, flags, ignore_index);
-  else CENET_LAUNCH((lv_keys_kernel<T, LV_MAXK>), pg, dim3(256), stream, inputs, labels, L.kA, L.pA, K, HW, gx, nl, per_image, flags, ignore_index);
+  CENET_LAUNCH_KM(lv_keys_kernel, T, K, pg, dim3(256), stream, inputs, labels, L.kA, L.pA, K, HW, gx, nl, per_image, flags, ignore_index);
   CENET_CHECK_LAUNCH();
-  const int rc = lv_sort(L, S, n, stream);
+  int rc = lv_sort(L, S, n, stream);
   if (rc != CENET_OK) return rc;
-  CENET_LAUNCH(lv_gcount_kernel, dim3(Tn, S), dim3(256), stream, (const unsigned*)L.pA, L.gcnt, n, Tn);
+  CENET_LAUNCH(tile_count_kernel<lv_is_g>, dim3(Tn, S), dim3(256), stream, (const unsigned*)L.pA, lv_is_g(), L.gcnt, n, Tn);
   CENET_CHECK_LAUNCH();
-  CENET_LAUNCH(lv_rowscan_kernel, lv_scan_grid(S, lv_scan_width(Tn)), dim3(256), stream, L.gcnt, L.G, (long)S, Tn, lv_scan_width(Tn));
-  CENET_CHECK_LAUNCH();
+  rc = tile_rowscan(L.gcnt, L.G, S, Tn, stream);
+  if (rc != CENET_OK) return rc;
   CENET_LAUNCH(lv_coef_kernel, dim3(Tn, S), dim3(256), stream, (const unsigned*)L.kA, (const unsigned*)L.pA, (const int*)L.gcnt,
                (const int*)L.G, coef, L.rows, n, Tn, B, K, HW, per_image, classes_all);
   CENET_CHECK_LAUNCH();
@@ -507,14 +411,12 @@ CENET_TWIN(lovasz_fwd, (const T* inputs, const float* labels, void* ws, long ws_
 template <typename T>
 static int lovasz_bwd_impl(const T* inputs, const float* coef, const float* gout, T* dinputs, int B, int K, int H, int W,
                            int from_probs, hipStream_t stream) {
-  if (B < 1 || K < 2 || K > LV_MAXK || H < 1 || W < 1 || (long)H * W >= (1L << 31)) return CENET_EINVAL;
+  if (B < 1 || K < 2 || K > PX_MAXK || H < 1 || W < 1 || (long)H * W >= (1L << 31)) return CENET_EINVAL;
   if (!inputs || !coef || !gout || !dinputs || (const void*)inputs == (const void*)dinputs) return CENET_EINVAL;
   const int HW = H * W, gx = cdiv(HW, 1024);
   if ((long)gx * B >= (1L << 31)) return CENET_EINVAL;
   const dim3 pg(gx * B);
-  if (K <= 4) CENET_LAUNCH((lv_bwd_kernel<T, 4>), pg, dim3(256), stream, inputs, coef, gout, dinputs, K, HW, gx, from_probs);
-  else if (K <= 9) CENET_LAUNCH((lv_bwd_kernel<T, 9>), pg, dim3(256), stream, inputs, coef, gout, dinputs, K, HW, gx, from_probs);
-  else CENET_LAUNCH((lv_bwd_kernel<T, LV_MAXK>), pg, dim3(256), stream, inputs, coef, gout, dinputs, K, HW, gx, from_probs);
+  CENET_LAUNCH_KM(lv_bwd_kernel, T, K, pg, dim3(256), stream, inputs, coef, gout, dinputs, K, HW, gx, from_probs);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
 }

@@ -10,10 +10,9 @@
 // the rows in a fixed order in double and writes the compact sums, the BoundaryDoU alpha and loss[0].  Every sum has one order of
 // additions whatever the arrival order of the workgroups, so loss and gradient are bitwise reproducible.  Stream order is the
 // only synchronisation.
-#include "common.h"
+#include "loss_pixel.h"
 #include "../../include/cenet_hip.h"
 
-#define SEGX_MAXK 16
 // workspace head: [0..K) I, [K..2K) Z, [2K..3K) Y, [3K..4K) S, [4K..5K) boundary pixel counts, [5K] ceN, [5K+1] ceD,
 // [5K+2..6K+2) BoundaryDoU alpha — what the backward kernel reads.  The rows of partials follow it.
 #define SEGX_HEAD 128
@@ -23,11 +22,11 @@ static inline int segx_fwd_it(int K) { return K > 9 ? 4 : 8; }  // pixels per th
 static inline long segx_rows(int B, int K, int HW) { return (long)cdiv(HW, 256 * segx_fwd_it(K)) * B; }
 
 extern "C" long cenet_seg_loss_ex_ws_floats(int B, int K, int H, int W) {
-  if (B <= 0 || K <= 0 || K > SEGX_MAXK || H <= 0 || W <= 0) return 0;
+  if (B <= 0 || K <= 0 || K > PX_MAXK || H <= 0 || W <= 0) return 0;
   return SEGX_HEAD + segx_rows(B, K, H * W) * (5 * K + 2);
 }
 
-// KM: compile-time bound of the class loops (4 / 9 / 16), as in loss_optim.hip.  cw: [2K] class weights (Dice, then CE) or NULL.
+// cw: [2K] class weights (Dice, then CE) or NULL.
 template <typename T, int KM>
 __global__ __launch_bounds__(256) void segx_fwd_kernel(const T* __restrict__ logits, const float* __restrict__ labels,
                                                       const float* __restrict__ cw, float* __restrict__ rows, int K, int HW,
@@ -55,9 +54,7 @@ __global__ __launch_bounds__(256) void segx_fwd_kernel(const T* __restrict__ log
       const int p = (blockIdx.x * IT + k0 + k) * 256 + threadIdx.x;
       pp[k] = p < HW ? p : -1;
       const int q = p < HW ? p : 0;
-#pragma unroll
-      for (int c = 0; c < KM; ++c)
-        if (c < K) vv[k][c] = ldf(lb0 + (long)c * HW + q);
+      px_load<KM>(vv[k], lb0, HW, q, K);
       tl[k] = lab[q];
     }
 #pragma unroll
@@ -66,26 +63,8 @@ __global__ __launch_bounds__(256) void segx_fwd_kernel(const T* __restrict__ log
       const int p = pp[k];
       const int t = (int)tl[k];
       if (has_ignore && t == ignore_index) continue;  // M = 0: the pixel adds to no sum
-      float v[KM];
-      float inv = 1.f;
-      if (!probs) {
-        float mx = -3.4e38f;
-#pragma unroll
-        for (int c = 0; c < KM; ++c)
-          if (c < K) mx = fmaxf(mx, vv[k][c]);
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < KM; ++c)
-          if (c < K) {
-            v[c] = fast_exp(vv[k][c] - mx);
-            s += v[c];
-          }
-        inv = fast_rcp(s);
-      } else {
-#pragma unroll
-        for (int c = 0; c < KM; ++c)
-          if (c < K) v[c] = vv[k][c];
-      }
+      float* v = vv[k];
+      if (!probs) px_softmax<KM, false>(v, K);
       bool edge = false;
       if (boundary) {  // a pixel of class t is a boundary pixel unless its four neighbours (zero padded) share t
         const int py = p / W, px = p - py * W;
@@ -95,7 +74,7 @@ __global__ __launch_bounds__(256) void segx_fwd_kernel(const T* __restrict__ log
 #pragma unroll
       for (int c = 0; c < KM; ++c)
         if (c < K) {
-          const float pc = v[c] * inv;
+          const float pc = v[c];
           part[KM + c] += pc * pc;
           part[3 * KM + c] += pc;
           if (c == t) {
@@ -133,7 +112,7 @@ __global__ __launch_bounds__(1024) void segx_finalize_kernel(float* __restrict__
                                                             const float* __restrict__ cw, long nrows, int K, float w_dice,
                                                             float w_ce, float w_bd, float w_jac, float smooth) {
   __shared__ double grp_sum[1024];
-  __shared__ double tot[5 * SEGX_MAXK + 2];
+  __shared__ double tot[5 * PX_MAXK + 2];
   const int NV = 5 * K + 2, G = 1024 / NV, t = threadIdx.x;
   const float* rows = ws + SEGX_HEAD;
   if (t < G * NV) {
@@ -218,46 +197,32 @@ __global__ __launch_bounds__(256) void segx_bwd_kernel(const T* __restrict__ log
     const int p = (blockIdx.x * IT + k) * 256 + threadIdx.x;
     pp[k] = p < HW ? p : -1;
     const int q = p < HW ? p : 0;
-#pragma unroll
-    for (int c = 0; c < KM; ++c)
-      if (c < K) vv[k][c] = ldf(lb0 + (long)c * HW + q);
+    px_load<KM>(vv[k], lb0, HW, q, K);
     tl[k] = lab[q];
   }
 #pragma unroll
   for (int k = 0; k < IT; ++k) {
     if (pp[k] < 0) continue;
     const int t = (int)tl[k];
+    float* v = vv[k];
     if (has_ignore && t == ignore_index) {  // exactly 0.0 in every class
 #pragma unroll
       for (int c = 0; c < KM; ++c)
         if (c < K) stf(db0 + (long)c * HW + pp[k], 0.f);
       continue;
     }
-    float v[KM];
     if (probs) {
 #pragma unroll
       for (int c = 0; c < KM; ++c)
-        if (c < K) stf(db0 + (long)c * HW + pp[k], go * (Bc[c] * vv[k][c] + (c == t ? A[c] : 0.f) + Cc[c]));
+        if (c < K) stf(db0 + (long)c * HW + pp[k], go * (Bc[c] * v[c] + (c == t ? A[c] : 0.f) + Cc[c]));
       continue;
     }
-    float mx = -3.4e38f;
-#pragma unroll
-    for (int c = 0; c < KM; ++c)
-      if (c < K) mx = fmaxf(mx, vv[k][c]);
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < KM; ++c)
-      if (c < K) {
-        v[c] = fast_exp(vv[k][c] - mx);
-        s += v[c];
-      }
-    const float inv = fast_rcp(s);
+    px_softmax<KM, false>(v, K);
     float gp[KM];
     float dot = 0.f, wt = 0.f;
 #pragma unroll
     for (int c = 0; c < KM; ++c)
       if (c < K) {
-        v[c] *= inv;
         gp[c] = Bc[c] * v[c] + (c == t ? A[c] : 0.f) + Cc[c];
         dot += gp[c] * v[c];
         if (c == t) wt = wc[c];
@@ -270,7 +235,7 @@ __global__ __launch_bounds__(256) void segx_bwd_kernel(const T* __restrict__ log
 }
 
 static int segx_check(int B, int K, int H, int W, float w_ce, float w_bd, float w_jac, int has_ignore, int from_probs) {
-  if (B <= 0 || K <= 0 || K > SEGX_MAXK || H <= 0 || W <= 0) return CENET_EINVAL;
+  if (B <= 0 || K <= 0 || K > PX_MAXK || H <= 0 || W <= 0) return CENET_EINVAL;
   if (B > 65535) return CENET_EUNSUPPORTED;
   if (from_probs && (w_ce != 0.f || w_bd != 0.f || w_jac != 0.f)) return CENET_EINVAL;  // DiceLoss(softmax=False) only
   if (has_ignore && w_bd != 0.f) return CENET_EUNSUPPORTED;  // a boundary count over a mask with holes is not defined
@@ -288,9 +253,7 @@ static int seg_loss_ex_fwd_impl(const T* logits, const float* labels, const floa
   const dim3 blocks(cdiv(HW, 256 * segx_fwd_it(K)), B);
   const int flags = (w_bd != 0.f ? SEGX_BOUNDARY : 0) | (has_ignore ? SEGX_IGNORE : 0) | (from_probs ? SEGX_PROBS : 0);
   float* rows = ws + SEGX_HEAD;
-  if (K <= 4) CENET_LAUNCH((segx_fwd_kernel<T, 4>), blocks, dim3(256), stream, logits, labels, cw, rows, K, HW, W, flags, ignore_index);
-  else if (K <= 9) CENET_LAUNCH((segx_fwd_kernel<T, 9>), blocks, dim3(256), stream, logits, labels, cw, rows, K, HW, W, flags, ignore_index);
-  else CENET_LAUNCH((segx_fwd_kernel<T, SEGX_MAXK>), blocks, dim3(256), stream, logits, labels, cw, rows, K, HW, W, flags, ignore_index);
+  CENET_LAUNCH_KM(segx_fwd_kernel, T, K, blocks, dim3(256), stream, logits, labels, cw, rows, K, HW, W, flags, ignore_index);
   CENET_LAUNCH(segx_finalize_kernel, dim3(1), dim3(1024), stream, ws, loss, cw, segx_rows(B, K, HW), K, w_dice, w_ce, w_bd, w_jac,
                smooth);
   CENET_CHECK_LAUNCH();
@@ -312,9 +275,8 @@ static int seg_loss_ex_bwd_impl(const T* logits, const float* labels, const floa
   const int HW = H * W;
   const dim3 blocks(cdiv(HW, 256 * 4), B);
   const int flags = (has_ignore ? SEGX_IGNORE : 0) | (from_probs ? SEGX_PROBS : 0);
-  if (K <= 4) CENET_LAUNCH((segx_bwd_kernel<T, 4>), blocks, dim3(256), stream, logits, labels, cw, ws, gout, dlogits, K, HW, w_dice, w_ce, w_bd, w_jac, smooth, flags, ignore_index);
-  else if (K <= 9) CENET_LAUNCH((segx_bwd_kernel<T, 9>), blocks, dim3(256), stream, logits, labels, cw, ws, gout, dlogits, K, HW, w_dice, w_ce, w_bd, w_jac, smooth, flags, ignore_index);
-  else CENET_LAUNCH((segx_bwd_kernel<T, SEGX_MAXK>), blocks, dim3(256), stream, logits, labels, cw, ws, gout, dlogits, K, HW, w_dice, w_ce, w_bd, w_jac, smooth, flags, ignore_index);
+  CENET_LAUNCH_KM(segx_bwd_kernel, T, K, blocks, dim3(256), stream, logits, labels, cw, ws, gout, dlogits, K, HW, w_dice, w_ce, w_bd, w_jac, smooth,
+                  flags, ignore_index);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
 }

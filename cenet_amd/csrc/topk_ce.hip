@@ -13,19 +13,16 @@
 //            to the digit at which the running count reaches the remaining quota, extends the prefix and takes what lies above
 //            off the quota.  Round 0 derives n_valid and m.  After round 3: the threshold key tau and r = how many of the pixels
 //            with key == tau are kept.  No key moves.
-//   tiecount, scan   pixels with key == tau per tile of TK_TILE elements, scanned over the tiles of a segment
-//   weights  rank among the ties = ties in earlier tiles + earlier in this tile (ballots and the lane number: no atomic decides
-//            an order); kept iff key > tau, or key == tau and rank < r; wgt = 1 / (m S_valid) or 0; one partial sum of the kept l
-//            per workgroup STORED as a row
-//   finalize one workgroup adds the rows in a fixed order in double (the pattern of seg_loss_ex.hip / dist_loss.hip / lovasz.hip)
+//   tiecount, scan   (tile_rank.h's tile_count_kernel<tk_is_tie>, tile_rowscan_kernel) pixels with key == tau per tile of TILE_ELEMS
+//            elements, scanned over the tiles of a segment
+//   weights  rank among the ties = ties in earlier tiles + earlier in this tile (tile_rank: ballots and the lane number, no atomic
+//            decides an order); kept iff key > tau, or key == tau and rank < r; wgt = 1 / (m S_valid) or 0; one partial sum of the
+//            kept l per workgroup STORED as a row (block_store_row)
+//   finalize one workgroup adds the rows in a fixed order in double (loss_pixel.h's rows_sum_f64)
 // No float atomics anywhere: loss, wgt and gradient have the same bits on every run.
-#include "common.h"
-#include "wave_ballot.h"
-#include "../../include/cenet_hip.h"
+#include "loss_pixel.h"
+#include "tile_rank.h"
 
-#define TK_MAXK 16
-#define TK_IT 8
-#define TK_TILE (256 * TK_IT)
 #define TK_BINS 256
 #define TK_ROUNDS 4
 #define TK_KEYS_IT 4     // pixels a thread of the keys pass takes
@@ -69,9 +66,7 @@ __global__ __launch_bounds__(256) void tk_keys_kernel(const T* __restrict__ in, 
     unsigned key = 0u;
     if (in_range) {
       float v[KM];
-#pragma unroll
-      for (int c = 0; c < KM; ++c)
-        if (c < K) v[c] = ldf(in0 + (long)c * HW + p);
+      px_load<KM>(v, in0, HW, p, K);
       const float t = lab[p];
       float mx = -3.4e38f;
 #pragma unroll
@@ -88,11 +83,11 @@ __global__ __launch_bounds__(256) void tk_keys_kernel(const T* __restrict__ in, 
         }
       const bool valid = hit && !(has_ignore && (int)t == ignore_index);
       const float l = fmaxf(logf(s) - xy, 0.f);
-      key = valid ? __float_as_uint(l) + 1u : 0u;
+      key = tile_key(l, valid);
       k0[p] = key;
       atomicAdd(&hist[key >> 24], 1);
     }
-    cnt += lv_popc(lv_ballot(key != 0u));
+    cnt += wave_popc(wave_ballot(key != 0u));
   }
   if ((threadIdx.x & 63) == 0) wvalid[threadIdx.x >> 6] = cnt;
   __syncthreads();
@@ -111,10 +106,10 @@ __global__ __launch_bounds__(256) void tk_value_keys_kernel(const float* __restr
   __syncthreads();
   for (int tile = blockIdx.x; tile < T; tile += gridDim.x) {
 #pragma unroll
-    for (int k = 0; k < TK_IT; ++k) {
-      const unsigned i = (unsigned)tile * TK_TILE + k * 256 + threadIdx.x;
+    for (int k = 0; k < TILE_IT; ++k) {
+      const unsigned i = (unsigned)tile * TILE_ELEMS + k * 256 + threadIdx.x;
       if (i < (unsigned)n) {
-        const unsigned key = __float_as_uint(values[(long)s * n + i]) + 1u;
+        const unsigned key = tile_key(values[(long)s * n + i], true);
         keys[(long)s * n + i] = key;
         atomicAdd(&hist[key >> 24], 1);
       }
@@ -138,8 +133,8 @@ __global__ __launch_bounds__(256) void tk_hist_kernel(const unsigned* __restrict
   const unsigned* k0 = keys + (long)s * n;
   for (int tile = blockIdx.x; tile < T; tile += gridDim.x) {
 #pragma unroll
-    for (int k = 0; k < TK_IT; ++k) {
-      const unsigned i = (unsigned)tile * TK_TILE + k * 256 + threadIdx.x;
+    for (int k = 0; k < TILE_IT; ++k) {
+      const unsigned i = (unsigned)tile * TILE_ELEMS + k * 256 + threadIdx.x;
       if (i < (unsigned)n) {
         const unsigned key = k0[i];
         if ((key >> (shift + 8)) == high) atomicAdd(&hist[(key >> shift) & (TK_BINS - 1)], 1);
@@ -183,7 +178,7 @@ __global__ __launch_bounds__(256) void tk_pick_kernel(const int* __restrict__ bi
   const int d = (TK_BINS - 1) - threadIdx.x;
   int c = 0;
   for (int j = 0; j < C; ++j) c += bins[tk_bins_at(s, round, j, C) + d];
-  int incl = lv_wave_incl_scan(c);
+  int incl = wave_incl_scan(c);
   if (lane == 63) wsum[wave] = incl;
   __syncthreads();
   for (int w = 0; w < wave; ++w) incl += wsum[w];
@@ -202,107 +197,58 @@ __global__ __launch_bounds__(256) void tk_pick_kernel(const int* __restrict__ bi
 }
 
 // ---- tie rank, weights, loss ----------------------------------------------------------------------------------------------------------
-// grid (T, S): tcnt[s T + tile] = keys of the tile equal to tau
-__global__ __launch_bounds__(256) void tk_tiecount_kernel(const unsigned* __restrict__ keys, const int* __restrict__ state,
-                                                         int* __restrict__ tcnt, int n, int T) {
-  __shared__ int wtot[4];
-  const int tile = blockIdx.x, s = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const unsigned tau = (unsigned)state[s * TK_STATE + TK_PREFIX];
-  const unsigned* k0 = keys + (long)s * n;
-  int cnt = 0;
-#pragma unroll
-  for (int k = 0; k < TK_IT; ++k) {
-    const unsigned i = (unsigned)tile * TK_TILE + k * 256 + threadIdx.x;
-    cnt += lv_popc(lv_ballot(i < (unsigned)n && k0[i] == tau));
-  }
-  if (lane == 0) wtot[wave] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) tcnt[(long)s * T + tile] = (wtot[0] + wtot[1]) + (wtot[2] + wtot[3]);
-}
-
-// grid (S), 256 threads: exclusive scan of tcnt[s T .. s T + T) in place, 256 values a step
-__global__ __launch_bounds__(256) void tk_scan_kernel(int* __restrict__ tcnt, int T) {
-  __shared__ int wsum[2][4];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  int* row = tcnt + (long)blockIdx.x * T;
-  int carry = 0, flip = 0;
-  for (int base = 0; base < T; base += 256, flip ^= 1) {  // (the same trip count for every thread)
-    const int i = base + threadIdx.x;
-    const int v = i < T ? row[i] : 0;
-    int incl = lv_wave_incl_scan(v);
-    if (lane == 63) wsum[flip][wave] = incl;
-    __syncthreads();  // (two copies of wsum taken in turn: one barrier a step is enough)
-    for (int w = 0; w < wave; ++w) incl += wsum[flip][w];
-    if (i < T) row[i] = carry + incl - v;
-    carry += (wsum[flip][0] + wsum[flip][1]) + (wsum[flip][2] + wsum[flip][3]);
-  }
-}
+// key == tau of the segment, for tile_count_kernel: tcnt[s T + tile] = keys of the tile equal to tau
+struct tk_is_tie {
+  const int* state;
+  __device__ unsigned seg(int s) const { return (unsigned)state[s * TK_STATE + TK_PREFIX]; }
+  __device__ bool operator()(unsigned key, unsigned tau) const { return key == tau; }
+};
 
 // grid (T, S).  Wave w owns elements [w 64 IT, (w + 1) 64 IT) of the tile, item k of lane l is element w 64 IT + 64 k + l: the order
-// (wave, item, lane) is the order of the pixel index.  tbase: tcnt scanned.  wgt / mask: either may be null.
+// (wave, item, lane) is the order of the pixel index.  tbase: tcnt scanned over the tiles.  wgt / mask: either may be null.
 __global__ __launch_bounds__(256) void tk_weights_kernel(const unsigned* __restrict__ keys, const int* __restrict__ state,
                                                         const int* __restrict__ tbase, const int* __restrict__ svalid,
                                                         float* __restrict__ wgt, unsigned char* __restrict__ mask,
                                                         float* __restrict__ rows, int n, int T) {
   __shared__ int wtot[4];
-  __shared__ float wred[4];
+  __shared__ float wred[4][1];
   const int tile = blockIdx.x, s = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const unsigned tau = (unsigned)state[s * TK_STATE + TK_PREFIX];
   const int r = state[s * TK_STATE + TK_QUOTA], m = state[s * TK_STATE + TK_M];
   const float w = m > 0 ? (float)(1.0 / ((double)m * (double)svalid[0])) : 0.f;
   const unsigned* k0 = keys + (long)s * n;
-  const unsigned start = (unsigned)tile * TK_TILE + wave * (64 * TK_IT) + lane;
-  const lv_mask_t below = ((lv_mask_t)1 << lane) - 1;
-  unsigned key[TK_IT];
-  int before[TK_IT];
-  int run = 0;
+  const unsigned start = (unsigned)tile * TILE_ELEMS + wave * (64 * TILE_IT) + lane;
+  unsigned key[TILE_IT];
+  int before[TILE_IT];
 #pragma unroll
-  for (int k = 0; k < TK_IT; ++k) {
-    const unsigned i = start + 64 * k;
-    key[k] = i < (unsigned)n ? k0[i] : 0u;
-    const lv_mask_t bal = lv_ballot(i < (unsigned)n && key[k] == tau);
-    before[k] = run + lv_popc(bal & below);
-    run += lv_popc(bal);
-  }
-  if (lane == 0) wtot[wave] = run;
-  __syncthreads();
-  int base = tbase[(long)s * T + tile];
-  for (int v = 0; v < wave; ++v) base += wtot[v];
-  float acc = 0.f;
+  for (int k = 0; k < TILE_IT; ++k) key[k] = start + 64 * k < (unsigned)n ? k0[start + 64 * k] : 0u;
+  const int base = tbase[(long)s * T + tile] +
+                   tile_rank<false>([&](int k) { return start + 64 * k < (unsigned)n && key[k] == tau; }, before, wtot);
+  float acc[1] = {0.f};
 #pragma unroll
-  for (int k = 0; k < TK_IT; ++k) {
+  for (int k = 0; k < TILE_IT; ++k) {
     const unsigned i = start + 64 * k;
     if (i >= (unsigned)n) continue;
     const bool kept = m > 0 && key[k] != 0u && (key[k] > tau || (key[k] == tau && base + before[k] < r));
-    if (kept) acc += __uint_as_float(key[k] - 1u);
+    if (kept) acc[0] += tile_key_value(key[k]);
     if (wgt) wgt[(long)s * n + i] = kept ? w : 0.f;
     if (mask) mask[(long)s * n + i] = kept ? 1 : 0;
   }
-  acc = wave_sum(acc);
-  if (lane == 0) wred[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) rows[(long)s * T + tile] = (wred[0] + wred[1]) + (wred[2] + wred[3]);
+  block_store_row(acc, wred, rows + (long)s * T + tile);
 }
 
-// one workgroup of 1024 threads: thread t adds rows t, t + 1024, ... over m_s S_valid in double, then a tree over the threads
+// the rows over m_s S_valid
 __global__ __launch_bounds__(1024) void tk_finalize_kernel(const float* __restrict__ rows, const int* __restrict__ state,
                                                           const int* __restrict__ svalid, float* __restrict__ loss, long nrows,
                                                           int T) {
-  __shared__ double acc[1024];
-  const int t = threadIdx.x;
+  __shared__ double acc[1][1024];
   const double sv = (double)svalid[0];
-  double sum = 0.0;
-  for (long r = t; r < nrows; r += 1024) {
+  double sum[1];
+  rows_sum_f64(acc, nrows, [&](long r, int) {
     const int m = state[(r / T) * TK_STATE + TK_M];
-    if (m > 0) sum += (double)rows[r] / ((double)m * sv);
-  }
-  acc[t] = sum;
-  __syncthreads();
-  for (int off = 512; off > 0; off >>= 1) {
-    if (t < off) acc[t] += acc[t + off];
-    __syncthreads();
-  }
-  if (t == 0) loss[0] = (float)acc[0];
+    return m > 0 ? (double)rows[r] / ((double)m * sv) : 0.0;  // (a sum that starts at +0 stays as it is under + 0)
+  }, sum);
+  if (threadIdx.x == 0) loss[0] = (float)sum[0];
 }
 
 // ---- backward ----------------------------------------------------------------------------------------------------------------------
@@ -328,23 +274,17 @@ __global__ __launch_bounds__(256) void tk_bwd_kernel(const T* __restrict__ in, c
     }
     const float t = labels[(long)b * HW + p];
     float v[KM];
-    float mx = -3.4e38f;
-#pragma unroll
-    for (int c = 0; c < KM; ++c)
-      if (c < K) mx = fmaxf(mx, v[c] = ldf(in0 + (long)c * HW + p));
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < KM; ++c)
-      if (c < K) s += v[c] = expf(v[c] - mx);
+    px_load<KM>(v, in0, HW, p, K);
+    px_softmax<KM, true>(v, K);
     const float gw = go * w;
 #pragma unroll
     for (int c = 0; c < KM; ++c)
-      if (c < K) stf(d0 + (long)c * HW + p, gw * (v[c] / s - (t == (float)c ? 1.f : 0.f)));
+      if (c < K) stf(d0 + (long)c * HW + p, gw * (v[c] - (t == (float)c ? 1.f : 0.f)));
   }
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
-extern "C" int cenet_topk_tile(void) { return TK_TILE; }
+extern "C" int cenet_topk_tile(void) { return TILE_ELEMS; }
 
 // the workspace, in 4-byte words: what the zero launch clears first — the bins [S, 4, C, 256], n_valid [S, C], S_valid [1] —, then the
 // state [S, 4], the tie counts [S, T], the loss rows [S, T] and the keys [S, n]
@@ -360,7 +300,7 @@ struct tk_ws_t {
   long zero_words, words;
 };
 static tk_ws_t tk_layout(void* ws, long S, long n) {
-  const long T = cdiv(n, TK_TILE);
+  const long T = cdiv(n, TILE_ELEMS);
   int* w = (int*)ws;
   tk_ws_t L;
   long at = 0;
@@ -381,30 +321,21 @@ static inline int tk_hist_wgs(int T, int S) {
   const int share = TK_HIST_WGS / S < 1 ? 1 : TK_HIST_WGS / S;
   return T < share ? T : share;
 }
-static inline bool tk_seg_ok(long S, long n) { return S >= 1 && S <= 65535 && n >= 1 && n < (1L << 31); }
-static inline bool tk_shape_ok(int B, int K, int H, int W, int per_image, long* S, long* n) {
-  if (B < 1 || K < 2 || K > TK_MAXK || H < 1 || W < 1) return false;
-  const long HW = (long)H * W;
-  if (HW >= (1L << 31)) return false;
-  *S = per_image ? B : 1;
-  *n = per_image ? HW : HW * B;
-  return tk_seg_ok(*S, *n);
-}
 
 extern "C" long cenet_topk_mask_ws_bytes(int S, int n) {
-  if (!tk_seg_ok(S, n)) return 0;
+  if (!tile_seg_ok(S, n)) return 0;
   return 4 * tk_layout(nullptr, S, n).words;
 }
 extern "C" long cenet_topk_ce_ws_bytes(int B, int H, int W, int per_image) {
   long S, n;
-  if (!tk_shape_ok(B, 2, H, W, per_image, &S, &n)) return 0;
+  if (!tile_seg_shape_ok(B, H, W, per_image, 1, &S, &n)) return 0;
   return 4 * tk_layout(nullptr, S, n).words;
 }
 
 // keys and the round-0 bins are in place -> state (tau, r, m), then wgt / mask and the loss rows
 static int tk_select(const tk_ws_t& L, const float* kpercent, const int* m_in, float* wgt, unsigned char* mask, int S, int n,
                      hipStream_t stream) {
-  const int T = cdiv(n, TK_TILE), C = tk_copies(S);
+  const int T = cdiv(n, TILE_ELEMS), C = tk_copies(S);
   for (int round = 0; round < TK_ROUNDS; ++round) {
     if (round > 0) {
       CENET_LAUNCH(tk_hist_kernel, dim3(tk_hist_wgs(T, S), S), dim3(256), stream, (const unsigned*)L.keys, (const int*)L.state, L.bins,
@@ -415,10 +346,10 @@ static int tk_select(const tk_ws_t& L, const float* kpercent, const int* m_in, f
                  m_in, n, round, C);
     CENET_CHECK_LAUNCH();
   }
-  CENET_LAUNCH(tk_tiecount_kernel, dim3(T, S), dim3(256), stream, (const unsigned*)L.keys, (const int*)L.state, L.tcnt, n, T);
+  CENET_LAUNCH(tile_count_kernel<tk_is_tie>, dim3(T, S), dim3(256), stream, (const unsigned*)L.keys, tk_is_tie{L.state}, L.tcnt, n, T);
   CENET_CHECK_LAUNCH();
-  CENET_LAUNCH(tk_scan_kernel, dim3(S), dim3(256), stream, L.tcnt, T);
-  CENET_CHECK_LAUNCH();
+  const int rc = tile_rowscan(L.tcnt, nullptr, S, T, stream);
+  if (rc != CENET_OK) return rc;
   CENET_LAUNCH(tk_weights_kernel, dim3(T, S), dim3(256), stream, (const unsigned*)L.keys, (const int*)L.state, (const int*)L.tcnt,
                (const int*)L.svalid, wgt, mask, L.rows, n, T);
   CENET_CHECK_LAUNCH();
@@ -427,11 +358,11 @@ static int tk_select(const tk_ws_t& L, const float* kpercent, const int* m_in, f
 
 extern "C" int cenet_topk_mask_f32(const float* values, const int* m, void* ws, long ws_bytes, unsigned char* mask, int S, int n,
                                    hipStream_t stream) {
-  if (!tk_seg_ok(S, n) || !values || !m || !ws || !mask || ws_bytes < cenet_topk_mask_ws_bytes(S, n)) return CENET_EINVAL;
+  if (!tile_seg_ok(S, n) || !values || !m || !ws || !mask || ws_bytes < cenet_topk_mask_ws_bytes(S, n)) return CENET_EINVAL;
   const tk_ws_t L = tk_layout(ws, S, n);
   int rc = cenet_zero_async((float*)L.bins, L.zero_words, stream);  // (the bits of 0.f are those of the integer 0)
   if (rc != CENET_OK) return rc;
-  const int T = cdiv(n, TK_TILE);
+  const int T = cdiv(n, TILE_ELEMS);
   CENET_LAUNCH(tk_value_keys_kernel, dim3(tk_hist_wgs(T, S), S), dim3(256), stream, values, L.keys, L.bins, n, T, tk_copies(S));
   CENET_CHECK_LAUNCH();
   return tk_select(L, nullptr, m, nullptr, mask, S, n, stream);
@@ -442,19 +373,17 @@ static int topk_ce_fwd_impl(const T* logits, const float* labels, const float* k
                             float* loss, int B, int K, int H, int W, int per_image, int has_ignore, int ignore_index,
                             hipStream_t stream) {
   long Sl, nl;
-  if (!tk_shape_ok(B, K, H, W, per_image, &Sl, &nl)) return CENET_EINVAL;
+  if (K < 2 || K > PX_MAXK || !tile_seg_shape_ok(B, H, W, per_image, 1, &Sl, &nl)) return CENET_EINVAL;
   if (!logits || !labels || !kpercent || !ws || !wgt || !loss || ws_bytes < cenet_topk_ce_ws_bytes(B, H, W, per_image))
     return CENET_EINVAL;
-  const int S = (int)Sl, n = (int)nl, HW = H * W, Tn = cdiv(n, TK_TILE), gx = cdiv(HW, 256 * TK_KEYS_IT);
+  const int S = (int)Sl, n = (int)nl, HW = H * W, Tn = cdiv(n, TILE_ELEMS), gx = cdiv(HW, 256 * TK_KEYS_IT);
   if ((long)gx * B >= (1L << 31)) return CENET_EINVAL;
   const tk_ws_t L = tk_layout(ws, S, n);
   int rc = cenet_zero_async((float*)L.bins, L.zero_words, stream);  // (the bits of 0.f are those of the integer 0)
   if (rc != CENET_OK) return rc;
   const dim3 pg(gx * B);
   const int C = tk_copies(S);
-  if (K <= 4) CENET_LAUNCH((tk_keys_kernel<T, 4>), pg, dim3(256), stream, logits, labels, L.keys, L.bins, L.nvalid, K, HW, gx, per_image, has_ignore, ignore_index, C);
-  else if (K <= 9) CENET_LAUNCH((tk_keys_kernel<T, 9>), pg, dim3(256), stream, logits, labels, L.keys, L.bins, L.nvalid, K, HW, gx, per_image, has_ignore, ignore_index, C);
-  else CENET_LAUNCH((tk_keys_kernel<T, TK_MAXK>), pg, dim3(256), stream, logits, labels, L.keys, L.bins, L.nvalid, K, HW, gx, per_image, has_ignore, ignore_index, C);
+  CENET_LAUNCH_KM(tk_keys_kernel, T, K, pg, dim3(256), stream, logits, labels, L.keys, L.bins, L.nvalid, K, HW, gx, per_image, has_ignore, ignore_index, C);
   CENET_CHECK_LAUNCH();
   rc = tk_select(L, kpercent, nullptr, wgt, nullptr, S, n, stream);
   if (rc != CENET_OK) return rc;
@@ -471,14 +400,12 @@ template <typename T>
 static int topk_ce_bwd_impl(const T* logits, const float* labels, const float* wgt, const float* gout, T* dlogits, int B, int K,
                             int H, int W, int has_ignore, int ignore_index, hipStream_t stream) {
   (void)has_ignore, (void)ignore_index;  // (an ignored pixel has wgt == 0 from the forward)
-  if (B < 1 || K < 2 || K > TK_MAXK || H < 1 || W < 1 || (long)H * W >= (1L << 31)) return CENET_EINVAL;
+  if (B < 1 || K < 2 || K > PX_MAXK || H < 1 || W < 1 || (long)H * W >= (1L << 31)) return CENET_EINVAL;
   if (!logits || !labels || !wgt || !gout || !dlogits || (const void*)logits == (const void*)dlogits) return CENET_EINVAL;
   const int HW = H * W, gx = cdiv(HW, 1024);
   if ((long)gx * B >= (1L << 31)) return CENET_EINVAL;
   const dim3 pg(gx * B);
-  if (K <= 4) CENET_LAUNCH((tk_bwd_kernel<T, 4>), pg, dim3(256), stream, logits, labels, wgt, gout, dlogits, K, HW, gx);
-  else if (K <= 9) CENET_LAUNCH((tk_bwd_kernel<T, 9>), pg, dim3(256), stream, logits, labels, wgt, gout, dlogits, K, HW, gx);
-  else CENET_LAUNCH((tk_bwd_kernel<T, TK_MAXK>), pg, dim3(256), stream, logits, labels, wgt, gout, dlogits, K, HW, gx);
+  CENET_LAUNCH_KM(tk_bwd_kernel, T, K, pg, dim3(256), stream, logits, labels, wgt, gout, dlogits, K, HW, gx);
   CENET_CHECK_LAUNCH();
   return CENET_OK;
 }

@@ -102,7 +102,7 @@ def test_mask_of_values_that_differ_in_the_lowest_byte_only(dev):
 
 
 def test_mask_over_more_tiles_than_a_scan_step_takes(dev):
-    """300 tiles: the scan of the tie counts over the tiles of a segment takes two steps of 256"""
+    """300 tiles: the scan of the tie counts over the tiles of a segment takes two steps of 64 lanes with four values each"""
     n = 300 * kern.topk_tile() + 3
     rng = np.random.default_rng(5)
     _check_mask(dev, (rng.integers(0, 1000, (1, n)) / 999).astype(np.float32), [n // 10], "thousand levels")

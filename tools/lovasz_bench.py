@@ -67,7 +67,7 @@ def counted_bytes(B, K, H, W, esz):
     """bytes per launch kind when every access misses the caches once; S n = B K H W (key, payload) pairs, T tiles a segment"""
     sn, T = B * K * H * W, -(-(B * H * W) // kern.lovasz_tile())
     return {"lv_keys_kernel": sn * esz + B * H * W * 4 + 8 * sn, "lv_hist_kernel": 4 * sn + 4 * K * 256 * T,
-            "lv_rowscan_kernel": 8 * K * 256 * T, "lv_scatter_kernel": 16 * sn + 4 * K * 256 * T, "lv_gcount_kernel": 4 * sn,
+            "tile_rowscan_kernel": 8 * K * 256 * T, "lv_scatter_kernel": 16 * sn + 4 * K * 256 * T, "tile_count_kernel": 4 * sn,
             "lv_coef_kernel": 12 * sn, "lv_bwd_kernel": sn * esz * 2 + 4 * sn}
 
 
@@ -147,11 +147,11 @@ def launches(dev, calls=10):
                     d["counted_bytes_per_launch"] = nbytes[kind]
                     # (the row scan: the bytes of the four digit-count scans over the time of all five — the fifth, of the g counts,
                     # moves a 256th of them —, so its rate reads slightly low)
-                    n_big = d["launches_per_call"] - 1 if kind == "lv_rowscan_kernel" else d["launches_per_call"]
+                    n_big = d["launches_per_call"] - 1 if kind == "tile_rowscan_kernel" else d["launches_per_call"]
                     d["TBs_on_counted_bytes"] = nbytes[kind] * n_big / (d["us_per_call"] * 1e-6) / 1e12
             row = {"shape": [B, K, H, W], "logits": str(dtype).replace("torch.", ""), "per_launch_kind": per,
                    "sum_us_per_call": sum(d["us_per_call"] for d in per.values()),
-                   "note": "lv_rowscan_kernel: bytes of the digit-count scans over the time of all scans, the g-count scan included"}
+                   "note": "tile_rowscan_kernel: bytes of the digit-count scans over the time of all scans, the g-count scan included"}
             rows.append(row)
             print(json.dumps(row), flush=True)
     if not all(r["per_launch_kind"] for r in rows):

@@ -51,11 +51,11 @@ def torch_topk_ce(x, lab, m, acc=torch.float32):
 def counted_bytes(B, K, H, W, esz, k=PERCENT):
     """bytes per launch kind when every access misses the caches once; the backward reads logits and labels of the kept pixels only"""
     px = B * H * W
-    return {"tk_keys_kernel": px * K * esz + 8 * px, "tk_hist_kernel": 4 * px, "tk_tiecount_kernel": 4 * px,
+    return {"tk_keys_kernel": px * K * esz + 8 * px, "tk_hist_kernel": 4 * px, "tile_count_kernel": 4 * px,
             "tk_weights_kernel": 8 * px, "tk_bwd_kernel": 4 * px + px * K * esz + int(k / 100 * (px * K * esz + 4 * px))}
 
 
-SMALL = ("tk_pick_kernel", "tk_scan_kernel", "tk_finalize_kernel", "zero")
+SMALL = ("tk_pick_kernel", "tile_rowscan_kernel", "tk_finalize_kernel", "zero")
 
 
 def fwd_bwd_fn(x, lab):
